@@ -4,13 +4,29 @@
 at bs=256/GPU, 512x512, T=40, bf16 (BASELINE.json configs[1]; configs[2] for
 --gpus 8 via torch.distributed.run).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One process per GPU (RCCL over xGMI for N > 1), W untimed warm-up steps (more,
 untimed, until --warmup-seconds have passed, the same count on every rank), then
 exactly K timed steps bracketed by barrier + synchronize; the max over ranks is
 reported.  `value` times the K steps on a batch resident in HBM when the clock
-starts (the bench contract: the PCIe-inclusive rate is never `value`).
+starts (the bench contract: the PCIe-inclusive rate is never `value`);
+`ms_per_step` is the same window per step.  A plain run does nothing else.
+
+--dump-outputs DIR: after the timed window the seeded initial training state
+(state dict, a fresh optimizer, the dropout / DropPath streams) is put back and
+the timed step function runs once more on the same batch; what that step hands
+its caller is written as DIR/<name>.npy (float32): loss, image_embeddings,
+text_embeddings, and a fixed seeded sample of the gradients and of the updated
+parameters (param_grads, params).  The state after the timed window itself
+cannot serve: the number of warm-up steps depends on the clock, and the
+summation order of the kernels' atomic reductions differs from run to run by
+rounding, which the AdamW steps before it amplify (a gradient near zero changes
+sign, the update changes by 2 lr).  One step from the seeded state has the same
+inputs in every run, so two runs, or two builds, can be compared output for
+output.
+
+--full adds everything below to the run and to the JSON line.
 `upload_prefetched` times the same K steps as SURVEY §8(d) writes the step,
 with the batch upload inside it: the collated batch (pinned host memory, uint8
 1-channel radiographs -- the data module's default -- or with --input fp32 the
@@ -18,7 +34,7 @@ reference's fp32 x-ray [B,3,H,W]; caption ids/masks [B,T] int64) goes up
 through src/data's DevicePrefetcher, which copies batch i+1 on a side stream
 while step i runs.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     : the dominant kernel (by total time) timed with HIP events on
                  its launch stream during the timed steps; achieved = its
                  algorithmic FLOPs / its summed launch duration
@@ -55,6 +71,14 @@ def parse():
                     help="after the W warm-up steps, keep stepping (untimed) until this many seconds of "
                          "warm-up have passed: r6 boxes ran the first ~2-3 s of a process's steady stepping "
                          "at a third of the rate")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, run the timed step once more from the seeded initial state and "
+                         "write what it computed (loss, embeddings, a seeded sample of gradients and updated "
+                         "parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline figure: upload_prefetched, "
+                         "roofline, serial_schedule, dp_schedule_1gpu, loss_delta_vs_fp32, pcie_inclusive, "
+                         "cpu_baseline, --kernel-report")
     ap.add_argument("--image-model", default="resnet34", choices=["resnet34", "nest_small"],
                     help="image tower: resnet34 (BASELINE configs[1]) or nest_small (configs[3], bs=128)")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 256; 128 for nest_small)")
@@ -92,6 +116,10 @@ def parse():
     ap.add_argument("--master-port", type=int, default=None,
                     help="rendezvous port when bench.py launches its own ranks (default: a free port)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.kernel_report and not a.full:
+        ap.error("--kernel-report needs --full (the report comes from the roofline pass)")
     nest = a.image_model != "resnet34"
     if a.batch is None:
         a.batch = 128 if nest else 256
@@ -447,6 +475,52 @@ def _traffic(family, dtype="bf16", image_model="resnet34"):
     return round(e["traffic_bytes_per_launch"]) if e else None
 
 
+def snapshot_state(model):
+    """The training state a step changes: parameters and BN statistics (the state
+    dict) and the towers' dropout / DropPath streams."""
+    towers = (model.image_encoder.model, model.text_encoder.model)
+    return {"sd": {k: v.detach().clone() for k, v in model.state_dict().items()},
+            "seed": [getattr(t, "_seed", None) for t in towers],
+            "gen": [t._gen.get_state() if hasattr(t, "_gen") else None for t in towers]}
+
+
+def restore_state(model, st):
+    """Put snapshot_state() back and return a fresh optimizer (zero moments, step 0)."""
+    model.load_state_dict(st["sd"])
+    for t, seed, gen in zip((model.image_encoder.model, model.text_encoder.model), st["seed"], st["gen"]):
+        if seed is not None:
+            t._seed = seed
+        if gen is not None:
+            t._gen.set_state(gen)
+    model.on_train_epoch_start()   # drops the embeddings cached by the steps so far
+    return model.configure_optimizers()["optimizer"]
+
+
+DUMP_SAMPLE = 4 << 20   # elements sampled from the flat parameters / gradients (16 MB each as float32)
+
+
+def dump_outputs(path, model, loss):
+    """What the step just run handed its caller, as <path>/<name>.npy (float32):
+    the loss, the embeddings training_step cached, and the same seeded sample of
+    positions from the gradients it left in p.grad and from the parameters the
+    optimizer then updated (all parameters, in model.parameters() order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cache = model.train_image_embeddings_and_labels_cached
+    params = list(model.parameters())
+    total = sum(p.numel() for p in params)
+    idx = torch.randint(0, total, (min(DUMP_SAMPLE, total),), generator=torch.Generator().manual_seed(2024))
+    idx = idx.sort().values.to(params[0].device)
+    flat = lambda ts: torch.cat([t.detach().float().reshape(-1) for t in ts])   # noqa: E731
+    out = {"loss": loss.detach().reshape(1),
+           "image_embeddings": cache["image_embedding"][-1],
+           "text_embeddings": cache["text_embedding"][-1],
+           "param_grads": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in params])[idx],
+           "params": flat(params)[idx]}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -456,7 +530,6 @@ def main():
         dry_run(args, rank, world)
         return
     from src.models.pretrain.VisionLanguageModule import VisionLanguageModule
-    from vlp_amd import ktimer
     import functools
 
     dev = torch.device("cuda", local)
@@ -485,7 +558,6 @@ def main():
     # where its launches do not share the CUs with the data-gradient chain.
     from vlp_amd import resnet34 as _r34
     from vlp_amd import clip_model as _cm
-    from vlp_amd._lib import lib as _vlib
     resnet = args.image_model == "resnet34"
     text_stream0 = _cm._USE_TEXT_STREAM
 
@@ -497,6 +569,9 @@ def main():
             _r34._USE_WG_STREAM = bool(on) and args.wgrad_stream
         _cm._USE_TEXT_STREAM = text_stream0 if on else False
     set_wgrad_stream(True)
+
+    # --dump-outputs steps once more from this state after the timed window
+    state0 = snapshot_state(model) if args.dump_outputs else None
 
     t_w = time.perf_counter()
     for _ in range(args.warmup):
@@ -512,21 +587,6 @@ def main():
         for _ in range(5):
             step()
         torch.cuda.synchronize()
-    # select the dominant kernel family to time (by total time in one serial step)
-    tk = args.roofline_kernel
-    if tk == "auto":
-        set_wgrad_stream(False)
-        ktimer.enable(None)
-        step()
-        torch.cuda.synchronize()
-        totals = ktimer.totals()
-        ktimer.disable()
-        set_wgrad_stream(True)
-        tk = max(totals, key=lambda k: totals[k][0]) if totals else None
-        if args.kernel_report and rank == 0:
-            with open(args.kernel_report, "w") as f:
-                json.dump({k: {"ms": v[0], "launches": v[1], "gflop": v[2] / 1e9}
-                           for k, v in sorted(totals.items(), key=lambda kv: -kv[1][0])}, f, indent=1)
 
     def timed(run):
         if world > 1:
@@ -548,6 +608,77 @@ def main():
     # host's PCIe / memory contention (r6: three boxes ran the prefetched window at
     # 2.2-4.7k pairs/s while the resident window beside it held 6.4-6.7k)
     el_hbm, loss = timed(lambda: [step() for _ in range(args.steps)][-1])
+    if args.dump_outputs:
+        # the timed step once more, from the seeded initial state: the same inputs in
+        # every run, whatever the warm-up and timed steps made of the weights
+        opt = restore_state(model, state0)
+        del state0
+        loss0 = step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, loss0)
+    pairs = world * args.batch * args.steps
+    value = pairs / el_hbm
+    peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
+    res = {
+        # BASELINE.json's metric is quoted at bs=256 (ResNet34); other batches name theirs
+        "metric": f"image-text pairs/sec (fwd+bwd) at bs={args.batch}/GPU, 1/2/4/8 MI355X",
+        "value": round(value, 2),
+        "unit": "image-text pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "warmup_seconds": args.warmup_seconds,
+        "ms_per_step": round(el_hbm / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": ("synthetic (seeded uint8 radiographs as "
+                 + ("the uint8 1-channel upload, normalised on the device"
+                    if args.input == "u8" else "the reference's normalised 3-ch fp32 tensor")
+                 + ", resident in HBM when the timed region starts; seeded token ids; random-init weights; "
+                   "the upload-inclusive rate is upload_prefetched, with --full)"),
+        "config": {"workload": ("ResNet34" if args.image_model == "resnet34" else "NesT-Small")
+                   + "+TinyBERT CLIP pretrain step (fwd+bwd+global-batch InfoNCE+AdamW)",
+                   "global_batch": world * args.batch, "per_gpu_batch": args.batch,
+                   "image_size": args.image_size, "seq_len": args.seq_len,
+                   "parallelism": f"dp{world}"},
+        "model_flops_frac": round(value * flop_per_pair(args) / (world * peak * 1e12), 4),
+        "loss": round(loss.item(), 5),
+    }
+    if args.full:
+        res.update(full_measurements(args, rank, world, dev, model, opt, timed, warm_more, set_wgrad_stream,
+                                     step, pairs, peak))
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, rank, world, dev, model, opt, timed, warm_more, set_wgrad_stream, step, pairs, peak):
+    """--full: everything the JSON line reports beside the headline figure, measured
+    after it in the same process (same model, optimizer and schedule switches);
+    returns the extra keys of the JSON line."""
+    from vlp_amd import ktimer
+    from vlp_amd._lib import lib as _vlib
+    resnet = args.image_model == "resnet34"
+    # select the dominant kernel family to time (by total time in one serial step)
+    tk = args.roofline_kernel
+    if tk == "auto":
+        set_wgrad_stream(False)
+        ktimer.enable(None)
+        step()
+        torch.cuda.synchronize()
+        totals = ktimer.totals()
+        ktimer.disable()
+        set_wgrad_stream(True)
+        tk = max(totals, key=lambda k: totals[k][0]) if totals else None
+        if args.kernel_report and rank == 0:
+            with open(args.kernel_report, "w") as f:
+                json.dump({k: {"ms": v[0], "launches": v[1], "gflop": v[2] / 1e9}
+                           for k, v in sorted(totals.items(), key=lambda kv: -kv[1][0])}, f, indent=1)
     # `upload_prefetched`: the SURVEY §8(d) step, batch upload included.  The
     # batch the data module collates (pinned host memory; the uint8 1-channel
     # radiograph, its default upload) reaches HBM through src/data's
@@ -609,76 +740,46 @@ def main():
     peak_meas = mfma_peak_measured(dev) if args.dtype == "bf16" else None
     ms_k, nl, flop_k = tot
     set_wgrad_stream(True)
-    if rank == 0:
-        pairs = world * args.batch * args.steps
-        value = pairs / el_hbm
-        peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
-        achieved = (flop_k / (ms_k / 1e3)) / 1e12 if ms_k > 0 else 0.0
-        res = {
-            # BASELINE.json's metric is quoted at bs=256 (ResNet34); other batches name theirs
-            "metric": f"image-text pairs/sec (fwd+bwd) at bs={args.batch}/GPU, 1/2/4/8 MI355X",
-            "value": round(value, 2),
-            "unit": "image-text pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "warmup_seconds": args.warmup_seconds,
-            "ms_per_step": round(el_hbm / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": ("synthetic (seeded uint8 radiographs as "
-                     + ("the uint8 1-channel upload, normalised on the device"
-                        if args.input == "u8" else "the reference's normalised 3-ch fp32 tensor")
-                     + ", resident in HBM when the timed region starts; seeded token ids; random-init weights; "
-                       "the upload-inclusive rate is upload_prefetched)"),
-            "config": {"workload": ("ResNet34" if args.image_model == "resnet34" else "NesT-Small")
-                       + "+TinyBERT CLIP pretrain step (fwd+bwd+global-batch InfoNCE+AdamW)",
-                       "global_batch": world * args.batch, "per_gpu_batch": args.batch,
-                       "image_size": args.image_size, "seq_len": args.seq_len,
-                       "parallelism": f"dp{world}"},
-            "model_flops_frac": round(value * flop_per_pair(args) / (world * peak * 1e12), 4),
-            "roofline": {"bound": "mfma", "kernel": tk, "achieved": round(achieved, 2), "peak": peak,
-                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                         "avg_launch_us": round(ms_k * 1e3 / max(nl, 1), 2), "launches": nl,
-                         "flop_per_launch": round(flop_k / max(nl, 1)), "peak_measured": peak_meas,
-                         "frac_of_measured": round(achieved / peak_meas, 4) if peak_meas else None,
-                         "traffic_unit": "HBM bytes/launch",
-                         "traffic": _traffic(tk, args.dtype, args.image_model),
-                         "timed_in": f"isolated pass of {args.roofline_steps} steps, serial schedule "
-                                     "(bracketed by vlp_trace_marker dispatches)"},
-            "loss": round(loss.item(), 5),
-            "upload_prefetched": {"value": round(pairs / el, 2), "ms_per_step": round(el / args.steps * 1e3, 3),
-                                  "note": "same K steps with the SURVEY 8(d) upload inside the timed region: the "
-                                          "batch collated in pinned host memory, copied per step by the side-stream "
-                                          "DevicePrefetcher (batch i+1 during step i)"},
-        }
-        ps = world * args.batch * args.roofline_steps
-        res["serial_schedule"] = {"value": round(ps / el_serial, 2),
-                                  "ms_per_step": round(el_serial / args.roofline_steps * 1e3, 3),
-                                  "steps": args.roofline_steps,
-                                  "note": "the roofline pass: same prefetched steps with the weight gradients and the "
-                                          "text tower on the main stream (no CU sharing); `value` uses the side streams"}
-        if shared is not None and shared[0] > 0:
-            res["roofline"]["achieved_under_default_schedule"] = round((shared[2] / (shared[0] / 1e3)) / 1e12, 2)
-        if rehearsal is not None:
-            # the rehearsal runs prefetched steps: compared with the prefetched windows
-            up = pairs / el
-            rehearsal["vs_upload_prefetched"] = round(rehearsal["value"] / up, 4)
-            # against the two plain runs bracketing it in time (the box drifts between runs)
-            rehearsal["vs_plain_mean"] = round(rehearsal["value"] / ((up + rehearsal["value_plain_rerun"]) / 2), 4)
-            res["dp_schedule_1gpu"] = rehearsal
-        if ldelta is not None:
-            res["loss_delta_vs_fp32"] = ldelta
-        if pcie is not None:
-            res["pcie_inclusive"] = pcie
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(args)
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank != 0:
+        return {}
+    achieved = (flop_k / (ms_k / 1e3)) / 1e12 if ms_k > 0 else 0.0
+    res = {
+        "roofline": {"bound": "mfma", "kernel": tk, "achieved": round(achieved, 2), "peak": peak,
+                     "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                     "avg_launch_us": round(ms_k * 1e3 / max(nl, 1), 2), "launches": nl,
+                     "flop_per_launch": round(flop_k / max(nl, 1)), "peak_measured": peak_meas,
+                     "frac_of_measured": round(achieved / peak_meas, 4) if peak_meas else None,
+                     "traffic_unit": "HBM bytes/launch",
+                     "traffic": _traffic(tk, args.dtype, args.image_model),
+                     "timed_in": f"isolated pass of {args.roofline_steps} steps, serial schedule "
+                                 "(bracketed by vlp_trace_marker dispatches)"},
+        "upload_prefetched": {"value": round(pairs / el, 2), "ms_per_step": round(el / args.steps * 1e3, 3),
+                              "note": "same K steps with the SURVEY 8(d) upload inside the timed region: the "
+                                      "batch collated in pinned host memory, copied per step by the side-stream "
+                                      "DevicePrefetcher (batch i+1 during step i)"},
+    }
+    ps = world * args.batch * args.roofline_steps
+    res["serial_schedule"] = {"value": round(ps / el_serial, 2),
+                              "ms_per_step": round(el_serial / args.roofline_steps * 1e3, 3),
+                              "steps": args.roofline_steps,
+                              "note": "the roofline pass: same prefetched steps with the weight gradients and the "
+                                      "text tower on the main stream (no CU sharing); `value` uses the side streams"}
+    if shared is not None and shared[0] > 0:
+        res["roofline"]["achieved_under_default_schedule"] = round((shared[2] / (shared[0] / 1e3)) / 1e12, 2)
+    if rehearsal is not None:
+        # the rehearsal runs prefetched steps: compared with the prefetched windows
+        up = pairs / el
+        rehearsal["vs_upload_prefetched"] = round(rehearsal["value"] / up, 4)
+        # against the two plain runs bracketing it in time (the box drifts between runs)
+        rehearsal["vs_plain_mean"] = round(rehearsal["value"] / ((up + rehearsal["value_plain_rerun"]) / 2), 4)
+        res["dp_schedule_1gpu"] = rehearsal
+    if ldelta is not None:
+        res["loss_delta_vs_fp32"] = ldelta
+    if pcie is not None:
+        res["pcie_inclusive"] = pcie
+    if world == 1 and not args.no_cpu_baseline:
+        res["cpu_baseline"] = cpu_baseline(args)
+    return res
 
 
 if __name__ == "__main__":

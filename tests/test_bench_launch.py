@@ -47,6 +47,15 @@ def test_bench_single_rank_dry_run():
     assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "dp1"
 
 
+def test_bench_kernel_report_needs_full():
+    # the kernel report comes from the --full passes: a plain run must refuse it, not drop it
+    r, lines = _run(["--dry-run", "--kernel-report", os.devnull])
+    assert r.returncode != 0 and not lines
+    assert "--full" in r.stderr
+    r, lines = _run(["--dry-run", "--full", "--kernel-report", os.devnull, "--steps", "2"])
+    assert r.returncode == 0 and len(lines) == 1, r.stderr[-2000:]
+
+
 def test_bench_child_failure_propagates():
     # a rank count that disagrees with WORLD_SIZE is refused by every rank: the
     # launcher must hand back a non-zero exit code, not swallow it

@@ -3,11 +3,13 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 TAG=${TAG:-r6}
+OUT=${OUT:-bench_out}   # where the logs go
+mkdir -p $OUT
 if [ -n "$TESTS" ]; then
-  timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest $TESTS -m gpu -x -q --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > gpurun_out/${TAG}_tests.log 2>&1 || { echo TESTS FAILED; tail -40 gpurun_out/${TAG}_tests.log; exit 1; }
-  tail -3 gpurun_out/${TAG}_tests.log
+  timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest $TESTS -m gpu -x -q --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > $OUT/${TAG}_tests.log 2>&1 || { echo TESTS FAILED; tail -40 $OUT/${TAG}_tests.log; exit 1; }
+  tail -3 $OUT/${TAG}_tests.log
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 600 python bench.py $BENCH_ARGS --kernel-report gpurun_out/${TAG}_kreport.json > gpurun_out/${TAG}_bench.log 2>&1 || { echo BENCH FAILED; tail -30 gpurun_out/${TAG}_bench.log; exit 1; }
-  tail -1 gpurun_out/${TAG}_bench.log
+  timeout -k 10 600 python bench.py --full $BENCH_ARGS --kernel-report $OUT/${TAG}_kreport.json > $OUT/${TAG}_bench.log 2>&1 || { echo BENCH FAILED; tail -30 $OUT/${TAG}_bench.log; exit 1; }
+  tail -1 $OUT/${TAG}_bench.log
 fi

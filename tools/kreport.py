@@ -1,4 +1,4 @@
-"""Pretty-print a bench.py --kernel-report JSON (per kernel family: time, launches, TF/s)."""
+"""Pretty-print a bench.py --full --kernel-report JSON (per kernel family: time, launches, TF/s)."""
 import json, sys
 d = json.load(open(sys.argv[1]))
 tot = sum(v["ms"] for v in d.values())

@@ -1,7 +1,7 @@
 """Average duration of the roofline kernel family's dispatches inside bench.py's
-isolated roofline pass, from a rocprofv3 kernel trace of the bench command.
+isolated roofline pass, from a rocprofv3 kernel trace of `bench.py --full`.
 
-bench.py brackets that pass with two empty marker dispatches
+With --full, bench.py brackets that pass with two empty marker dispatches
 (vlp_trace_marker -> trace_marker_begin_kernel / trace_marker_end_kernel); the
 dispatches of the family (kernel names matching --include and not --exclude)
 that start between the markers are the launches the bench line's
