@@ -695,10 +695,13 @@ def test_linear_wgrad(ops, dt, shape):
 
 
 @pytest.mark.parametrize("dt", DT)
-@pytest.mark.parametrize("M,N,K", [(512, 1152, 384), (300, 384, 1536)])
+@pytest.mark.parametrize("M,N,K", [(512, 1152, 384), (300, 384, 1536), (1100, 1152, 384)])
 def test_linear_fwd_dgrad_large(ops, dt, M, N, K):
-    """y = x W^T + b and dx = dy W at NesT level-2 sizes (M, N, K >= 256: the 256x256
-    ping-pong kernel in bf16; M = 300 ends in a partial tile) against fp32 math."""
+    """y = x W^T + b and dx = dy W at NesT level-2 widths against fp32 math.  M <= 1024
+    takes the 64x256 kernel (M = 300 ends in a partial tile); M = 1100 with
+    N, K >= 256 and K % 64 == 0 takes the 256x256 ping-pong kernel in bf16, forward
+    and data gradient, with partial M and N tiles.  tests/test_gpu_linear_routes.py
+    covers the remaining routes and epilogues with a per-element gate."""
     torch.manual_seed(8)
     x = torch.randn(M, K).to(dt).float()
     w = (torch.randn(N, K) * K ** -0.5).to(dt).float()

@@ -24,8 +24,9 @@ namespace vlp {
 // Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, branch-free: one reciprocal and
 // one exp): 1 - erf(z) = P(t) exp(-z^2), t = 1 / (1 + p z), z = |x| / sqrt 2 >= 0.
 // The tail 1 - erf is formed directly (no cancellation for x < 0); the result is
-// within 3.3e-7 absolute of the exact GELU over [-12, 12], as close as
-// 0.5 * x * (1 + erff(.)) in fp32 (4.5e-7), at a third of its VALU cost (the
+// within 3.4e-7 absolute of the exact GELU over [-12, 12] (measured on the device:
+// 3.30e-7 forward, 2.39e-7 for the gradient; tests/test_gpu_linear_routes.py), as close
+// as 0.5 * x * (1 + erff(.)) in fp32 (4.5e-7), at a third of its VALU cost (the
 // library erff is two branchy polynomials; the NesT fc1 epilogue spent more time
 // in it than in the GEMM).  exp(-z^2) = exp(-x^2 / 2) is also the Gaussian
 // density's exponential, shared by the gradient.
@@ -815,12 +816,23 @@ __global__ void scatter_rows_kernel(int R, int D, const T* __restrict__ in, int 
 
 using namespace vlp;
 
+// The K-contiguous loaders (KMat) move whole 16-byte chunks (8 bf16 / 4 fp32) and
+// zero-fill a chunk only when its FIRST element lies outside [M) x [K): a reduction
+// depth that ends inside a chunk would fold the next row's leading elements into
+// the sum, and a leading dimension that is no chunk multiple misaligns every other
+// row's 16-byte loads.  The entry points refuse both instead of returning numbers.
+static bool lin_kchunks_ok(int dtype, int K, int ld) {
+  const int e = dtype == VLP_BF16 ? 8 : 4;
+  return K > 0 && K % e == 0 && ld % e == 0;
+}
+
 // y[M][N] = x[M][K] W[N][K]^T (+bias) with epilogue mode (see EpiLinear).
 VLP_EXPORT int vlp_linear_fwd(int dtype, int M, int N, int K, const void* x, int ldx, const void* w,
                               const float* bias, void* y, int ldy, int mode, void* aux,
                               const void* res, int ldr, float p, unsigned long long seed,
                               void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!lin_kchunks_ok(dtype, K, ldx)) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) {
     // the bf16 row-chunk epilogue moves 8-column groups with 16-B accesses
     if (N % 8 || ldy % 8 || (res && ldr % 8)) return (int)hipErrorInvalidValue;
@@ -841,7 +853,7 @@ VLP_EXPORT int vlp_linear_fwd_rs(int dtype, int M, int N, int K, const void* x, 
                                  const float* bias, void* y, int ldy, const void* res, int ldr,
                                  const float* rscale, int rps, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (!rscale || rps < 1) return (int)hipErrorInvalidValue;
+  if (!rscale || rps < 1 || !lin_kchunks_ok(dtype, K, ldx)) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) {
     if (N % 8 || ldy % 8 || ldr % 8) return (int)hipErrorInvalidValue;
     KMat<bf16> la{(const bf16*)x, ldx, M, K};
@@ -860,6 +872,7 @@ VLP_EXPORT int vlp_linear_dgrad(int dtype, int M, int Kin, int Nout, const void*
                                 const void* w, void* dx, int lddx, int mode, const void* aux,
                                 int ldaux, const void* addend, int ldad, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!lin_kchunks_ok(dtype, Nout, lddy)) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) {
     if (Kin % 8 || lddx % 8 || (aux && ldaux % 8) || (addend && ldad % 8)) return (int)hipErrorInvalidValue;
     KMat<bf16> la{(const bf16*)dy, lddy, M, Nout};
@@ -929,6 +942,9 @@ VLP_EXPORT int vlp_linear_wgrad_ws(int dtype, int M, int Nout, int Kin, const vo
                                    void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (dtype != VLP_BF16 || Kin % 4 || !ws) return (int)hipErrorInvalidValue;
+  // MN-contiguous operands: 16-byte chunks run along Nout / Kin (a tail chunk only feeds
+  // rows / columns the epilogue masks), but every token row must start 16-byte aligned
+  if (lddy % 8 || ldx % 8) return (int)hipErrorInvalidValue;
   // each split reduces >= VLP_LINW_WS_ROWS token rows: the text tower runs on a
   // side stream beside the image tower, where CU time per FLOP (prologue,
   // epilogue, slab traffic), not latency, is what the step pays for
