@@ -50,6 +50,16 @@ int vlp_trace_marker(int end, void* stream);
  * (VisionLanguageModule.py:30-35 -> ImageEncoder.forward).
  * Weight operands are produced by vlp_pack_conv:
  *   wp = [Co][KH][KW][C]   (forward),  wt = [C][KH][KW][Co]   (data gradient).
+ * Channel counts: C and Co must both be whole 16-byte chunks -- multiples of 8 in
+ * bf16, of 4 in fp32.  The loaders resolve (pixel, filter tap) from a chunk's first
+ * element and the epilogues store 4- or 8-column groups, so any other count would
+ * mix the neighbouring pixel's channels into the sum; vlp_conv_fwd, vlp_conv_dgrad,
+ * vlp_conv_dgrad_relu, vlp_conv_wgrad and vlp_conv_wgrad_ws return
+ * hipErrorInvalidValue for it (the stem, with 3 input channels, has its own entry
+ * points below).  The bf16 data gradients further need Co % 64 == 0 (one filter tap
+ * per 64-deep K-step); the fused variants state their own shapes.
+ * Operand sizes: every activation tensor must stay below 2 GiB (32-bit buffer
+ * offsets); the forward and data-gradient entry points do not check this.
  */
 /* y[N][Ho][Wo][Co] = conv(x, w); optionally x := relu(in_scale*x + in_shift)
  * per input channel on load (previous BN+ReLU); accumulates per-channel

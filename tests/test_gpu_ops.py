@@ -64,12 +64,13 @@ CONV_CASES = [
     (4, 8, 8, 320, 256, 3, 3, 1, 1),
     (2, 12, 12, 128, 128, 3, 3, 1, 1),  # Co = 128 weight gradient: 128x384 ping-pong tiles
     (3, 9, 11, 256, 320, 3, 3, 1, 1),
-    # LDS-window kernel (bf16 3x3 stride 1, W in {16, 32, 64}, C and the GEMM N multiples of 128):
-    # one window per 256-pixel tile of whole rows, several N tiles, NC = 2 / 4 / 8 channel chunks
+    # LDS-window kernel (bf16 3x3 stride 1, W = 16 or 64 at the default VLP_WIN_WIDTHS, C and the
+    # GEMM N multiples of 128): one window per 256-pixel tile of whole rows, several N tiles,
+    # NC = 2 / 4 / 8 channel chunks
     (2, 8, 64, 128, 128, 3, 3, 1, 1),
     (3, 4, 64, 256, 128, 3, 3, 1, 1),
     (2, 8, 64, 128, 256, 3, 3, 1, 1),
-    (2, 16, 32, 256, 256, 3, 3, 1, 1),
+    (2, 16, 32, 256, 256, 3, 3, 1, 1),  # W = 32 is not a window width by default: 256x256 ping-pong kernel
     (2, 16, 16, 512, 512, 3, 3, 1, 1),
 ]
 

@@ -2609,10 +2609,21 @@ __global__ void __launch_bounds__(256) stem1_wgrad_fold_kernel(int ks, const flo
 
 using namespace vlp;
 
+// Every loader here resolves (pixel, filter tap) from the FIRST element of a 16-byte
+// chunk (ConvFwdA::load, ConvDgradA::load, ConvWgradB::fixed, MNMat) and every epilogue
+// stores groups of 4 or 8 columns, so a channel count that is no whole number of chunks
+// (8 bf16 / 4 fp32) lets a chunk straddle a tap or a row and take the neighbouring
+// pixel's channels.  The entry points refuse such shapes instead.
+static bool conv_chunks_ok(int dtype, int C, int Co) {
+  const int e = dtype == VLP_BF16 ? 8 : 4;
+  return C > 0 && Co > 0 && C % e == 0 && Co % e == 0;
+}
+
 VLP_EXPORT int vlp_conv_fwd(int dtype, const void* x, const void* wp, void* y, int N, int H, int W,
                             int C, int Co, int KH, int KW, int S, int P, const float* in_scale,
                             const float* in_shift, double* stat_sum, double* stat_sumsq,
                             int stat_rep, void* stream) {
+  if (!conv_chunks_ok(dtype, C, Co)) return (int)hipErrorInvalidValue;
   ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VLP_BF16)
@@ -2710,6 +2721,7 @@ VLP_EXPORT int vlp_conv_dgrad(int dtype, const void* dy, const void* wt, void* d
                               const float* bn_shift, const float* bn_mean,
                               const float* bn_invstd, double* stat1, double* stat2,
                               int stat_rep, void* stream) {
+  if (!conv_chunks_ok(dtype, C, Co)) return (int)hipErrorInvalidValue;
   ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VLP_BF16)
@@ -2726,7 +2738,8 @@ VLP_EXPORT int vlp_conv_dgrad_relu(int dtype, const void* dy, const void* wt, vo
                                    double* stat2, int stat_rep, void* stream) {
   ConvGeom geo = make_geom(N, H, W, C, Co, KH, KW, S, P);
   hipStream_t st = (hipStream_t)stream;
-  if ((relu_out == nullptr) == (relu_mask == nullptr) || C % 8) return (int)hipErrorInvalidValue;
+  if ((relu_out == nullptr) == (relu_mask == nullptr) || C % 8 || !conv_chunks_ok(dtype, C, Co))
+    return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16)
     return conv_dgrad_relu_t<bf16>(dy, wt, g, geo, addend, relu_out, relu_mask, y, mean, invstd, stat1, stat2,
                                    stat_rep, st);
@@ -2788,6 +2801,7 @@ VLP_EXPORT int vlp_conv_wgrad(int dtype, const void* dy, const void* x, float* d
   ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
   hipStream_t st = (hipStream_t)stream;
   if ((long long)N * H * W * C >= (1ll << 31)) return (int)hipErrorInvalidValue;   // 32-bit pixel walk
+  if (!conv_chunks_ok(dtype, C, Co)) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) return conv_wgrad_t<bf16>(dy, x, dw_ws, g, in_scale, in_shift, st);
   return conv_wgrad_t<float>(dy, x, dw_ws, g, in_scale, in_shift, st);
 }
@@ -2797,7 +2811,8 @@ VLP_EXPORT int vlp_conv_wgrad_ws(int dtype, const void* dy, const void* x, float
                                  void* stream) {
   ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
   hipStream_t st = (hipStream_t)stream;
-  if (!nsplit || (long long)N * H * W * C >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (!nsplit || (long long)N * H * W * C >= (1ll << 31) || !conv_chunks_ok(dtype, C, Co))
+    return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) return conv_wgrad_ws_t<bf16>(dy, x, split_ws, ws_floats, nsplit, g, st);
   return conv_wgrad_ws_t<float>(dy, x, split_ws, ws_floats, nsplit, g, st);
 }
