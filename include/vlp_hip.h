@@ -303,8 +303,9 @@ int vlp_maxpool_bwd_apply(int dtype, int N, int H, int W, int C, const void* dp,
                           const double* sum_g, const double* sum_gx, void* dy, void* stream);
 int vlp_avgpool_fwd(int dtype, int N, int HW, int C, const void* x, void* feat, void* stream);
 
-/* ---------------- text tower (TinyBERT) ----------------
- * Replace the cuBLAS/ATen kernels of HF BertModel (VisionLanguageModule.py:45, :57-60). */
+/* ---------------- text towers (TinyBERT, DistilBERT) ----------------
+ * Replace the cuBLAS/ATen kernels of HF BertModel / DistilBertModel
+ * (VisionLanguageModule.py:43-45, :57-60). */
 /* y = x W^T + bias; mode 0 plain, 1 aux = pre-activation & y = gelu(aux),
  * 2 y = dropout_p(x W^T + bias) + res.  bf16 (also _rs and vlp_linear_dgrad): the
  * output width and every output/operand leading dimension a multiple of 8 and the
@@ -333,6 +334,8 @@ int vlp_linear_wgrad_ws(int dtype, int M, int Nout, int Kin, const void* dy, int
 int vlp_linear_wgrad_ws_floats(int M, int Nout, int Kin, long long* n);
 /* out[n] += sum_m x[m][n] (bias gradients; fp32 atomics) */
 int vlp_colsum(int dtype, int M, int N, const void* x, int ld, float* out, void* stream);
+/* LayerNorm over rows of D <= 1024 (D a multiple of 8 for bf16, 4 for fp32), else
+ * hipErrorInvalidValue */
 int vlp_layernorm_fwd(int dtype, int M, int D, const void* x, const float* gamma,
                       const float* beta, float eps, void* y, float* mean, float* rstd, float p,
                       unsigned long long seed, void* stream);
@@ -349,11 +352,14 @@ int vlp_layernorm_bwd_add(int dtype, int M, int D, const void* dy, const void* x
 int vlp_layernorm_bwd_add_rs(int dtype, int M, int D, const void* dy, const void* x, const float* mean,
                              const float* rstd, const float* gamma, const void* addend, void* dx, void* dxs,
                              const float* rscale, int rps, float* dgamma, float* dbeta, void* stream);
+/* softmax attention of one (sequence, head) per workgroup: T <= 64, 1 <= dh <= 64 (head
+ * channels padded to 32 or 64 in LDS), else hipErrorInvalidValue */
 int vlp_attn_fwd(int dtype, int B, int T, int H, int dh, const void* qkv, const long long* amask,
                  void* ctx, float* P, float scale, float p, unsigned long long seed, void* stream);
 int vlp_attn_bwd(int dtype, int B, int T, int H, int dh, const void* qkv, const float* P,
                  const void* dctx, void* dqkv, float scale, float p, unsigned long long seed,
                  void* stream);
+/* temb / dtemb NULL: a model without a token-type table (DistilBERT) */
 int vlp_embed_fwd(int dtype, int M, int T, int D, const long long* ids, const long long* tt,
                   const float* wemb, const float* pemb, const float* temb, void* e_out,
                   void* stream);

@@ -210,7 +210,7 @@ static int gemm_lin(int M, int N, int K, int ksplit, const LA& la, const LB& lb,
 
 // ---------------- LayerNorm over rows of D ----------------
 // 16 lanes per row, 16-B chunks: lane j of a row owns chunks j, j+16, ...
-// (NCH of them, D = 8 * chunks for bf16 / 4 * chunks for fp32, D <= 512), so
+// (NCH of them, D = 8 * chunks for bf16 / 4 * chunks for fp32, D <= 1024), so
 // a row is read once into registers and reduced with four 16-lane shuffles.
 // fp32 statistics; mean / rstd saved per row.
 // sum over a 16-lane row, result in every lane (DPP row_ror 8 / 4, then two
@@ -301,7 +301,10 @@ layernorm_bwd_kernel(int M, int D, const T* __restrict__ dy, float p_out, uint64
                      float* dgamma, float* dbeta, const T* __restrict__ addend,
                      const float* __restrict__ rscale, int rps) {
   constexpr int E = Chunk<T>::N;
-  __shared__ float part[NW][2][512];
+  // columns one block can hold: 512 up to D = 512 (the NesT / TinyBERT
+  // instantiations, unchanged), the instantiation's own 16 * NCH * E above
+  constexpr int PD = 16 * NCH * E > 512 ? 16 * NCH * E : 512;
+  __shared__ float part[NW][2][PD];
   const int j = threadIdx.x & 15, w = threadIdx.x >> 6;
   const int nch = D / E;
   float pg[NCH][E], pb[NCH][E], gm[NCH][E];
@@ -450,7 +453,7 @@ colsum_vec_kernel(int M, int N, const bf16* __restrict__ x, int ld, float* __res
 // BertSelfAttention (transformers, called through VisionLanguageModule.py:45,
 // 57-60): S = Q K^T * scale + ext_mask, P = softmax(S), P' = dropout(P),
 // ctx = P' V.  ONE WAVE per (sequence b, head h): the token dimension is padded
-// to TB*16 (T <= 64) and the head dimension (26 for TinyBERT) to 32, and every
+// to TB*16 (T <= 64) and the head dimension (26 for TinyBERT) to DP, and every
 // product is a chain of 16x16 MFMA tiles on LDS-staged operands:
 //   bf16: v_mfma_f32_16x16x32_bf16 (one K-step of 32),
 //   fp32 (parity mode): v_mfma_f32_16x16x4f32 x 4 per K-step of 16 (exact fp32 fma).
@@ -463,8 +466,28 @@ colsum_vec_kernel(int M, int N, const bf16* __restrict__ x, int ld, float* __res
 // The masked-key bias is HF's: scores + finfo(fp32).min where attention_mask == 0
 // (modeling_bert get_extended_attention_mask); padded key slots (j >= T) are -inf.
 // P (fp32, pre-dropout, [B][H][T][T]) is saved for the backward.
+//
+// The head dimension is padded to a compile-time extent DP: 32 for dh <= 32
+// (TinyBERT, static LDS, as before) and 64 for 32 < dh <= 64 (DistilBERT /
+// BERT-base heads of 64).  Channels d >= dh of every image are zero, so the
+// padding adds nothing to any product, and the stores mask d < dh.
+// LDS budget in bytes per workgroup (TB = 3 for T <= 48, TB = 4 for T <= 64;
+// image rows are DP or the token K-extent wide plus one 16-B pad, AttnGeom).
+// Forward images: Q, K, V^T, P'.  Backward: V, dO, K^T, Q^T, dO^T, dS, dS^T, P'^T.
+//                 forward                  backward
+//   DP   T   TB   bf16      fp32           bf16      fp32
+//   32  <=48  3   19 200    30 464         42 240    63 744
+//   32  <=64  4   24 064    44 544         51 712    96 768
+//   64  <=48  3   29 952    49 408         62 208    96 000
+//   64  <=64  4   36 864    69 632         73 728   139 264
+// The DP = 32 kernels keep their static images.  Every DP = 64 kernel takes its
+// images from dynamic LDS sized by AttnGeom::kFwdBytes / kBwdBytes, and the
+// launchers raise the per-kernel dynamic limit once per device through
+// prepare_kernel (gemm.h) where that is above 64 KB.  The largest, the fp32
+// (parity mode) backward at T > 48, uses 139 264 of gfx950's 163 840 B, one
+// workgroup per CU; the bf16 backward keeps two per CU at either tile.
 constexpr int kMaxT = 64;
-constexpr int kMaxDh = 32;
+constexpr int kMaxDh = 64;
 
 template <typename T> struct AttnMma;
 template <> struct AttnMma<bf16> {
@@ -499,18 +522,26 @@ __device__ __forceinline__ float q4_sum(float v) {
   return v + __shfl_xor(v, 32, 64);
 }
 
-// LDS image geometry (elements): rows of a "k = head channel" image hold DP = 32
+// LDS image geometry (elements): rows of a "k = head channel" image hold DP
 // values (+ pad), rows of a "k = token" image TPK = TB*16 values, rounded up to
 // the MFMA K-step (+ pad); pads keep 16-B row alignment and spread LDS banks.
-template <typename T, int TB>
+template <typename T, int TB, int DP>
 struct AttnGeom {
+  static_assert(DP == 32 || DP == 64, "padded head extent");
   static constexpr int TP = TB * 16;                                   // padded tokens
   static constexpr int KS = AttnMma<T>::KS;
   static constexpr int TK = (TP + KS - 1) / KS * KS;                   // token-k extent
   static constexpr int PADE = 16 / (int)sizeof(T);                     // one 16-B pad
-  static constexpr int LD = 32 + PADE;                                 // k = channel
+  static constexpr int LD = DP + PADE;                                 // k = channel
   static constexpr int LT = TK + PADE;                                 // k = token
+  static constexpr bool kDyn = DP > 32;                                // images in dynamic LDS
+  static constexpr int kFwdBytes = (2 * TP * LD + DP * LT + TP * LT) * (int)sizeof(T);
+  static constexpr int kBwdBytes = (2 * TP * LD + 3 * DP * LT + 3 * TP * LT) * (int)sizeof(T);
+  static_assert(kFwdBytes <= 160 * 1024 && kBwdBytes <= 160 * 1024, "LDS budget");
 };
+
+// the DP = 64 kernels' images (dynamic LDS; one symbol for every instantiation)
+extern __shared__ __attribute__((aligned(16))) unsigned char attn_dyn_lds[];
 
 template <typename T>
 __device__ __forceinline__ void zero_lds(T* p, int n) {
@@ -538,23 +569,32 @@ __device__ __forceinline__ void load_head(T* dst, int ld, bool transpose, const 
 template <int TB>
 constexpr int attn_waves() { return VLP_ATTN_MW ? TB : 1; }
 
-template <typename T, int TB>
+template <typename T, int TB, int DP>
 __global__ void __launch_bounds__(256)
 attn_fwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const int64_t* __restrict__ amask,
                 T* __restrict__ ctx, float* __restrict__ P, float scale, float p, uint64_t seed) {
-  using G = AttnGeom<T, TB>;
+  using G = AttnGeom<T, TB, DP>;
   using M = AttnMma<T>;
-  __shared__ __attribute__((aligned(16))) T sQ[G::TP * G::LD];
-  __shared__ __attribute__((aligned(16))) T sK[G::TP * G::LD];
-  __shared__ __attribute__((aligned(16))) T sVt[32 * G::LT];   // V^T: [d][j]
-  __shared__ __attribute__((aligned(16))) T sP[G::TP * G::LT];  // P': [i][j]
+  T *sQ, *sK, *sVt, *sP;
+  if constexpr (G::kDyn) {
+    sQ = reinterpret_cast<T*>(attn_dyn_lds);
+    sK = sQ + G::TP * G::LD;
+    sVt = sK + G::TP * G::LD;
+    sP = sVt + DP * G::LT;
+  } else {
+    __shared__ __attribute__((aligned(16))) T aQ[G::TP * G::LD];
+    __shared__ __attribute__((aligned(16))) T aK[G::TP * G::LD];
+    __shared__ __attribute__((aligned(16))) T aVt[DP * G::LT];   // V^T: [d][j]
+    __shared__ __attribute__((aligned(16))) T aP[G::TP * G::LT];  // P': [i][j]
+    sQ = aQ; sK = aK; sVt = aVt; sP = aP;
+  }
   const int b = blockIdx.x / H, h = blockIdx.x - (blockIdx.x / H) * H;
   const int Dm = H * dh;
   const size_t ld = 3 * (size_t)Dm;
   const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
   zero_lds(sQ, G::TP * G::LD);
   zero_lds(sK, G::TP * G::LD);
-  zero_lds(sVt, 32 * G::LT);
+  zero_lds(sVt, DP * G::LT);
   zero_lds(sP, G::TP * G::LT);
   __syncthreads();
   const T* base = qkv + (size_t)b * Tn * ld + h * dh;
@@ -580,7 +620,7 @@ attn_fwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const i
     for (int jb = 0; jb < TB; ++jb) {
       s[jb] = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k0 = 0; k0 < 32; k0 += M::KS) M::mma(s[jb], sK, G::LD, jb * 16, sQ, G::LD, ib * 16, k0);
+      for (int k0 = 0; k0 < DP; k0 += M::KS) M::mma(s[jb], sK, G::LD, jb * 16, sQ, G::LD, ib * 16, k0);
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -622,7 +662,7 @@ attn_fwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const i
   for (int ib = wv; ib < TB; ib += NW) {
     const int i = ib * 16 + li;
 #pragma unroll
-    for (int db = 0; db < 2; ++db) {
+    for (int db = 0; db < DP / 16; ++db) {
       v4f o = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k0 = 0; k0 < G::TK; k0 += M::KS) M::mma(o, sVt, G::LT, db * 16, sP, G::LT, ib * 16, k0);
@@ -641,29 +681,42 @@ attn_fwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const i
 // Backward of attn_fwd_kernel, one wave per (b, h):
 //   dP' = dctx V^T ; dP = dP' * dropout mask ; dS = P (dP - rowsum(P dP))
 //   dq = scale * dS K ;  dk = scale * dS^T Q ;  dv = P'^T dctx
-template <typename T, int TB>
+template <typename T, int TB, int DP>
 __global__ void __launch_bounds__(256)
 attn_bwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const float* __restrict__ P,
                 const T* __restrict__ dctx, T* __restrict__ dqkv, float scale, float p, uint64_t seed) {
-  using G = AttnGeom<T, TB>;
+  using G = AttnGeom<T, TB, DP>;
   using M = AttnMma<T>;
-  __shared__ __attribute__((aligned(16))) T sV[G::TP * G::LD];     // V: [j][d]
-  __shared__ __attribute__((aligned(16))) T sdO[G::TP * G::LD];    // dctx: [i][d]
-  __shared__ __attribute__((aligned(16))) T sKt[32 * G::LT];       // K^T: [d][j]
-  __shared__ __attribute__((aligned(16))) T sQt[32 * G::LT];       // Q^T: [d][i]
-  __shared__ __attribute__((aligned(16))) T sdOt[32 * G::LT];      // dctx^T: [d][i]
-  __shared__ __attribute__((aligned(16))) T sdS[G::TP * G::LT];    // dS: [i][j]
-  __shared__ __attribute__((aligned(16))) T sdSt[G::TP * G::LT];   // dS^T: [j][i]
-  __shared__ __attribute__((aligned(16))) T sPdt[G::TP * G::LT];   // P'^T: [j][i]
+  T *sV, *sdO, *sKt, *sQt, *sdOt, *sdS, *sdSt, *sPdt;
+  if constexpr (G::kDyn) {
+    sV = reinterpret_cast<T*>(attn_dyn_lds);
+    sdO = sV + G::TP * G::LD;
+    sKt = sdO + G::TP * G::LD;
+    sQt = sKt + DP * G::LT;
+    sdOt = sQt + DP * G::LT;
+    sdS = sdOt + DP * G::LT;
+    sdSt = sdS + G::TP * G::LT;
+    sPdt = sdSt + G::TP * G::LT;
+  } else {
+    __shared__ __attribute__((aligned(16))) T aV[G::TP * G::LD];     // V: [j][d]
+    __shared__ __attribute__((aligned(16))) T adO[G::TP * G::LD];    // dctx: [i][d]
+    __shared__ __attribute__((aligned(16))) T aKt[DP * G::LT];       // K^T: [d][j]
+    __shared__ __attribute__((aligned(16))) T aQt[DP * G::LT];       // Q^T: [d][i]
+    __shared__ __attribute__((aligned(16))) T adOt[DP * G::LT];      // dctx^T: [d][i]
+    __shared__ __attribute__((aligned(16))) T adS[G::TP * G::LT];    // dS: [i][j]
+    __shared__ __attribute__((aligned(16))) T adSt[G::TP * G::LT];   // dS^T: [j][i]
+    __shared__ __attribute__((aligned(16))) T aPdt[G::TP * G::LT];   // P'^T: [j][i]
+    sV = aV; sdO = adO; sKt = aKt; sQt = aQt; sdOt = adOt; sdS = adS; sdSt = adSt; sPdt = aPdt;
+  }
   const int b = blockIdx.x / H, h = blockIdx.x - (blockIdx.x / H) * H;
   const int Dm = H * dh;
   const size_t ld = 3 * (size_t)Dm;
   const int l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
   zero_lds(sV, G::TP * G::LD);
   zero_lds(sdO, G::TP * G::LD);
-  zero_lds(sKt, 32 * G::LT);
-  zero_lds(sQt, 32 * G::LT);
-  zero_lds(sdOt, 32 * G::LT);
+  zero_lds(sKt, DP * G::LT);
+  zero_lds(sQt, DP * G::LT);
+  zero_lds(sdOt, DP * G::LT);
   zero_lds(sdS, G::TP * G::LT);
   zero_lds(sdSt, G::TP * G::LT);
   zero_lds(sPdt, G::TP * G::LT);
@@ -687,7 +740,7 @@ attn_bwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const f
     for (int jb = 0; jb < TB; ++jb) {
       dp[jb] = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k0 = 0; k0 < 32; k0 += M::KS) M::mma(dp[jb], sV, G::LD, jb * 16, sdO, G::LD, ib * 16, k0);
+      for (int k0 = 0; k0 < DP; k0 += M::KS) M::mma(dp[jb], sV, G::LD, jb * 16, sdO, G::LD, ib * 16, k0);
     }
     float pr[TB][4], pd[TB][4];
     float dot = 0.f;
@@ -719,7 +772,7 @@ attn_bwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const f
   for (int nb = wv; nb < TB; nb += NW) {
     const int t = nb * 16 + li;
 #pragma unroll
-    for (int db = 0; db < 2; ++db) {
+    for (int db = 0; db < DP / 16; ++db) {
       v4f dq = v4f{0.f, 0.f, 0.f, 0.f}, dk = dq, dv = dq;
 #pragma unroll
       for (int k0 = 0; k0 < G::TK; k0 += M::KS) {
@@ -745,6 +798,8 @@ attn_bwd_kernel(int B, int Tn, int H, int dh, const T* __restrict__ qkv, const f
 
 // ---------------- embeddings ----------------
 // e = word[ids] + pos[t] + type[tt]; h = dropout(LN(e)); saves e (T) for backward.
+// DistilBERT (transformers modeling_distilbert Embeddings) has no token-type
+// table: temb == nullptr / dtemb == nullptr leave that term and its gradient out.
 template <typename T>
 __global__ void embed_fwd_kernel(int M, int Tn, int D, const int64_t* __restrict__ ids,
                                  const int64_t* __restrict__ tt, const float* __restrict__ wemb,
@@ -755,7 +810,8 @@ __global__ void embed_fwd_kernel(int M, int Tn, int D, const int64_t* __restrict
   int64_t id = ids[row];
   int64_t ty = tt ? tt[row] : 0;
   for (int c = threadIdx.x; c < D; c += blockDim.x) {
-    float s = wemb[(size_t)id * D + c] + pemb[(size_t)t * D + c] + temb[(size_t)ty * D + c];
+    float s = wemb[(size_t)id * D + c] + pemb[(size_t)t * D + c];
+    if (temb) s += temb[(size_t)ty * D + c];   // no table (DistilBERT): no token-type term
     e_out[(size_t)row * D + c] = from_f<T>(s);
   }
 }
@@ -799,8 +855,10 @@ embed_pt_bwd_kernel(int B, int Tn, int D, const int64_t* __restrict__ tt, const 
 #pragma unroll
     for (int q = 0; q < 4; ++q) { a += part[q][0][l]; b0 += part[q][1][l]; b1 += part[q][2][l]; }
     atomicAdd(dpemb + (size_t)t * D + c, a);
-    atomicAdd(dtemb + c, b0);
-    if (b1 != 0.f) atomicAdd(dtemb + D + c, b1);
+    if (dtemb) {   // no token-type table: no gradient for it
+      atomicAdd(dtemb + c, b0);
+      if (b1 != 0.f) atomicAdd(dtemb + D + c, b1);
+    }
   }
 }
 
@@ -1008,9 +1066,10 @@ static void ln_fwd_t(int M, int D, const void* x, const float* gamma, const floa
                      beta, eps, (T*)y, mean, rstd, p, (uint64_t)seed);
 }
 // chunks per lane: ceil(D / (16 elements-per-chunk... x 16 lanes))
+constexpr int kMaxLnD = 1024;
 static int ln_nch(int dtype, int D) {
   const int e = dtype == VLP_BF16 ? 8 : 4;
-  if (D < 1 || D > 512 || D % e) return -1;
+  if (D < 1 || D > kMaxLnD || D % e) return -1;
   return (D / e + 15) / 16;
 }
 #define LN_DISPATCH(F, dtype, nch, ...)                                                          \
@@ -1020,7 +1079,9 @@ static int ln_nch(int dtype, int D) {
         case 1: F<bf16, 1>(__VA_ARGS__); break;                                                \
         case 2: F<bf16, 2>(__VA_ARGS__); break;                                                \
         case 3: F<bf16, 3>(__VA_ARGS__); break;                                                \
-        default: F<bf16, 4>(__VA_ARGS__); break;                                               \
+        case 4: F<bf16, 4>(__VA_ARGS__); break;                                                \
+        case 5: case 6: F<bf16, 6>(__VA_ARGS__); break;                                        \
+        default: F<bf16, 8>(__VA_ARGS__); break;                                               \
       }                                                                                        \
     } else {                                                                                   \
       switch (nch) {                                                                           \
@@ -1029,7 +1090,9 @@ static int ln_nch(int dtype, int D) {
         case 3: F<float, 3>(__VA_ARGS__); break;                                               \
         case 4: F<float, 4>(__VA_ARGS__); break;                                               \
         case 5: case 6: F<float, 6>(__VA_ARGS__); break;                                       \
-        default: F<float, 8>(__VA_ARGS__); break;                                              \
+        case 7: case 8: F<float, 8>(__VA_ARGS__); break;                                       \
+        case 9: case 10: case 11: case 12: F<float, 12>(__VA_ARGS__); break;                   \
+        default: F<float, 16>(__VA_ARGS__); break;                                             \
       }                                                                                        \
     }                                                                                          \
   } while (0)
@@ -1058,16 +1121,22 @@ static void ln_bwd_t(int M, int D, const void* dy, float p_out, unsigned long lo
   // the cap applies to text-sized M only: NesT's 0.1-2 M token rows need the
   // wide grid for bandwidth (a 160 or M/2048 cap there: -3 % per NesT step)
   constexpr int cap = 160;   // LayerNorm-backward grid cap for text-sized M (atomic fan-in)
-  if (M <= 65536 && VLP_LNB_TEXT_WAVES > 4) {
-    // text-sized M: the capped grid with 8-wave blocks (32 rows per pass, twice the
-    // loads in flight per CU at the same atomic fan-in)
-    constexpr int NW = VLP_LNB_TEXT_WAVES;
-    int blocks = (M + NW * 4 - 1) / (NW * 4);
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((layernorm_bwd_kernel<T, NCH, NW>), dim3(blocks), dim3(NW * 64), 0, st, M, D, (const T*)dy,
-                       p_out, (uint64_t)seed_out, (const T*)x, mean, rstd, gamma, (T*)dx, (T*)dxd, p_in,
-                       (uint64_t)seed_in, dgamma, dbeta, (const T*)addend, rscale, rps);
-    return;
+  // rows wider than 512 (D = 768: 48 values per lane in each of five register
+  // arrays) need more than the 256 registers a lane has in an 8-wave block:
+  // they take the 4-wave block below (512 registers per lane, no scratch)
+  constexpr bool wide_rows = 16 * NCH * Chunk<T>::N > 512;
+  if constexpr (VLP_LNB_TEXT_WAVES > 4 && !wide_rows) {
+    if (M <= 65536) {
+      // text-sized M: the capped grid with 8-wave blocks (32 rows per pass, twice the
+      // loads in flight per CU at the same atomic fan-in)
+      constexpr int NW = VLP_LNB_TEXT_WAVES;
+      int blocks = (M + NW * 4 - 1) / (NW * 4);
+      if (blocks > cap) blocks = cap;
+      hipLaunchKernelGGL((layernorm_bwd_kernel<T, NCH, NW>), dim3(blocks), dim3(NW * 64), 0, st, M, D, (const T*)dy,
+                         p_out, (uint64_t)seed_out, (const T*)x, mean, rstd, gamma, (T*)dx, (T*)dxd, p_in,
+                         (uint64_t)seed_in, dgamma, dbeta, (const T*)addend, rscale, rps);
+      return;
+    }
   }
   int blocks = (M + 15) / 16;
   const int lim = M <= 65536 ? cap : 4096;
@@ -1114,33 +1183,53 @@ VLP_EXPORT int vlp_layernorm_bwd_add_rs(int dtype, int M, int D, const void* dy,
                               addend, rscale, rps, stream);
 }
 
-template <typename T, int TB>
-static void launch_attn_fwd(int B, int Tn, int H, int dh, const void* qkv, const long long* amask, void* ctx,
-                            float* P, float scale, float p, unsigned long long seed, hipStream_t st) {
-  hipLaunchKernelGGL((attn_fwd_kernel<T, TB>), dim3(B * H), dim3(64 * attn_waves<TB>()), 0, st, B, Tn, H, dh, (const T*)qkv,
-                     (const int64_t*)amask, (T*)ctx, P, scale, p, (uint64_t)seed);
+// DP = 32: static images, launched as before.  DP = 64: dynamic images; the
+// per-kernel limit is raised once per device (KernelDevState), never per launch.
+template <typename T, int TB, int DP>
+static int launch_attn_fwd(int B, int Tn, int H, int dh, const void* qkv, const long long* amask, void* ctx,
+                           float* P, float scale, float p, unsigned long long seed, hipStream_t st) {
+  using G = AttnGeom<T, TB, DP>;
+  int lds = 0;
+  if constexpr (G::kDyn) {
+    static KernelDevState kst;
+    lds = G::kFwdBytes;
+    const int e = prepare_kernel(kst, (const void*)&attn_fwd_kernel<T, TB, DP>, lds, 0, nullptr);
+    if (e) return e;
+  }
+  hipLaunchKernelGGL((attn_fwd_kernel<T, TB, DP>), dim3(B * H), dim3(64 * attn_waves<TB>()), lds, st, B, Tn, H, dh,
+                     (const T*)qkv, (const int64_t*)amask, (T*)ctx, P, scale, p, (uint64_t)seed);
+  return (int)hipGetLastError();
 }
-template <typename T, int TB>
-static void launch_attn_bwd(int B, int Tn, int H, int dh, const void* qkv, const float* P, const void* dctx,
-                            void* dqkv, float scale, float p, unsigned long long seed, hipStream_t st) {
-  hipLaunchKernelGGL((attn_bwd_kernel<T, TB>), dim3(B * H), dim3(64 * attn_waves<TB>()), 0, st, B, Tn, H, dh, (const T*)qkv, P,
-                     (const T*)dctx, (T*)dqkv, scale, p, (uint64_t)seed);
+template <typename T, int TB, int DP>
+static int launch_attn_bwd(int B, int Tn, int H, int dh, const void* qkv, const float* P, const void* dctx,
+                           void* dqkv, float scale, float p, unsigned long long seed, hipStream_t st) {
+  using G = AttnGeom<T, TB, DP>;
+  int lds = 0;
+  if constexpr (G::kDyn) {
+    static KernelDevState kst;
+    lds = G::kBwdBytes;
+    const int e = prepare_kernel(kst, (const void*)&attn_bwd_kernel<T, TB, DP>, lds, 0, nullptr);
+    if (e) return e;
+  }
+  hipLaunchKernelGGL((attn_bwd_kernel<T, TB, DP>), dim3(B * H), dim3(64 * attn_waves<TB>()), lds, st, B, Tn, H, dh,
+                     (const T*)qkv, P, (const T*)dctx, (T*)dqkv, scale, p, (uint64_t)seed);
+  return (int)hipGetLastError();
 }
+// (dtype, token tile, padded head extent) -> instantiation; F is launch_attn_fwd / _bwd
+#define ATTN_DISPATCH(F, dtype, small, wide, ...)                                                \
+  ((dtype) == VLP_BF16                                                                           \
+       ? ((wide) ? ((small) ? F<bf16, 3, 64>(__VA_ARGS__) : F<bf16, 4, 64>(__VA_ARGS__))         \
+                 : ((small) ? F<bf16, 3, 32>(__VA_ARGS__) : F<bf16, 4, 32>(__VA_ARGS__)))        \
+       : ((wide) ? ((small) ? F<float, 3, 64>(__VA_ARGS__) : F<float, 4, 64>(__VA_ARGS__))       \
+                 : ((small) ? F<float, 3, 32>(__VA_ARGS__) : F<float, 4, 32>(__VA_ARGS__))))
 
 VLP_EXPORT int vlp_attn_fwd(int dtype, int B, int Tn, int H, int dh, const void* qkv,
                             const long long* amask, void* ctx, float* P, float scale, float p,
                             unsigned long long seed, void* stream) {
   if (Tn < 1 || Tn > kMaxT || dh < 1 || dh > kMaxDh || B < 1 || H < 1) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const bool small = Tn <= 48;
-  if (dtype == VLP_BF16) {
-    if (small) launch_attn_fwd<bf16, 3>(B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
-    else launch_attn_fwd<bf16, 4>(B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
-  } else {
-    if (small) launch_attn_fwd<float, 3>(B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
-    else launch_attn_fwd<float, 4>(B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
-  }
-  return (int)hipGetLastError();
+  const bool small = Tn <= 48, wide = dh > 32;
+  return ATTN_DISPATCH(launch_attn_fwd, dtype, small, wide, B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
 }
 
 VLP_EXPORT int vlp_attn_bwd(int dtype, int B, int Tn, int H, int dh, const void* qkv, const float* P,
@@ -1148,15 +1237,8 @@ VLP_EXPORT int vlp_attn_bwd(int dtype, int B, int Tn, int H, int dh, const void*
                             unsigned long long seed, void* stream) {
   if (Tn < 1 || Tn > kMaxT || dh < 1 || dh > kMaxDh || B < 1 || H < 1) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const bool small = Tn <= 48;
-  if (dtype == VLP_BF16) {
-    if (small) launch_attn_bwd<bf16, 3>(B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
-    else launch_attn_bwd<bf16, 4>(B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
-  } else {
-    if (small) launch_attn_bwd<float, 3>(B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
-    else launch_attn_bwd<float, 4>(B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
-  }
-  return (int)hipGetLastError();
+  const bool small = Tn <= 48, wide = dh > 32;
+  return ATTN_DISPATCH(launch_attn_bwd, dtype, small, wide, B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
 }
 
 VLP_EXPORT int vlp_embed_fwd(int dtype, int M, int Tn, int D, const long long* ids,

@@ -5,14 +5,14 @@ Same import path (`_target_: src.models.pretrain.VisionLanguageModule.VisionLang
 configs/model/vision_language.yaml:1), same classes (ImageEncoder :27-35,
 TextEncoder :38-60, VisionLanguageModule :63-705), same constructor kwargs
 (including the misspelt `image_encoder_droupout`, :83), same hooks and
-state-dict keys (image_encoder.model.<timm>, text_encoder.model.<HF Bert>,
+state-dict keys (image_encoder.model.<timm>, text_encoder.model.<HF Bert / DistilBert>,
 image_projection, text_projection, logit_scale).  All arithmetic runs in the
 HIP kernels of libvlp_hip.so (vlp_amd); there is no CPU fallback.
 
 Additions (keyword-only, defaults keep reference behaviour where possible):
   compute_dtype  "fp32" (the reference's arithmetic, default) | "bf16" (throughput mode,
                  the _mi355x experiments; src/train.py also derives it from trainer.precision)
-  text_dropout   TinyBERT hidden/attention dropout (reference: 0.1 from the hub config)
+  text_dropout   text tower hidden/attention dropout (reference: 0.1 from the hub configs)
   fused_optimizer  build vlp_amd.FusedAdamW when the configured optimizer is
                    torch.optim.AdamW (same hyper-parameters / param groups)
   device         where the parameter arenas live (default: cuda)
@@ -40,6 +40,7 @@ from vlp_amd.clip_model import ClipHead, ClipStepFn, _project_normalize, role_we
 from vlp_amd.optim import FusedAdamW  # noqa: E402
 from vlp_amd.nest import NEST_CFGS, NestTower  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
+from vlp_amd.distilbert import DistilBertConfig, DistilBertTower  # noqa: E402
 from vlp_amd.tinybert import TinyBertConfig, TinyBertTower  # noqa: E402
 
 logger = logging.getLogger("project")
@@ -109,19 +110,26 @@ class ImageEncoder(nn.Module):
         return self.model(x)
 
 
+# text_encoder_model -> the tower's hidden size (the text_embedding_dim the projection needs)
+TEXT_HIDDEN = {"distilbert": 768, "tinybert": 312}
+
+
 class TextEncoder(nn.Module):
-    """:38-60 — TinyBERT; returns the CLS token's last hidden state."""
+    """:38-60 — DistilBERT (:43, the reference's default) or TinyBERT (:45); returns the
+    CLS token's last hidden state."""
 
     def __init__(self, text_encoder_model, compute_dtype="fp32", device=None, dropout=0.1):
         super().__init__()
         if text_encoder_model == "distilbert":
-            raise NotImplementedError("TextEncoder: distilbert is outside the MI355X hot path (use tinybert)")
-        if text_encoder_model != "tinybert":
+            self.model = DistilBertTower(DistilBertConfig(dropout, dropout), compute_dtype=compute_dtype,
+                                         device=device)
+        elif text_encoder_model == "tinybert":
+            self.model = TinyBertTower(TinyBertConfig(dropout, dropout), compute_dtype=compute_dtype,
+                                       device=device)
+        else:
             raise ValueError(
                 f"VisionLanguageModule: Text encoder model {text_encoder_model} is not supported. "
                 f"Supported models are: distilbert, tinybert.")
-        self.model = TinyBertTower(TinyBertConfig(dropout, dropout), compute_dtype=compute_dtype,
-                                   device=device)
         self.target_token_idx = 0
         self.model.train()
 
@@ -292,9 +300,11 @@ class VisionLanguageModule(_Base):
             enc_kw["drop_path_rate"] = kwargs["drop_path_rate"]
         self.image_encoder = ImageEncoder(image_model, compute_dtype=compute_dtype, device=dev, **enc_kw)
         feat_dim = self.image_encoder.model.num_features if image_model != "resnet34" else 512
-        if image_embedding_dim != feat_dim or text_embedding_dim != 312:
-            raise ValueError(f"MI355X build: {image_model} ({feat_dim}) + tinybert (312) feature dims, got "
-                             f"image_embedding_dim={image_embedding_dim}, text_embedding_dim={text_embedding_dim}")
+        text_dim = TEXT_HIDDEN.get(text_encoder_model)   # unknown names: TextEncoder's ValueError below
+        if image_embedding_dim != feat_dim or (text_dim is not None and text_embedding_dim != text_dim):
+            raise ValueError(f"MI355X build: {image_model} ({feat_dim}) + {text_encoder_model} ({text_dim}) feature "
+                             f"dims, got image_embedding_dim={image_embedding_dim}, "
+                             f"text_embedding_dim={text_embedding_dim}")
         self.text_encoder = TextEncoder(text_encoder_model, compute_dtype=compute_dtype, device=dev,
                                         dropout=text_dropout)                        # :99
         # projections + logit scale (:102-111) live in one arena; registered here so

@@ -40,6 +40,16 @@ class _Holder(nn.Module):
 
 
 class TinyBertTower(ArenaModule):
+    # arena names the forward / backward drivers use for one encoder layer (HF
+    # BertModel's here; DistilBertTower maps HF DistilBertModel's onto the same drivers)
+    _LAYER = "encoder.layer.{}."
+    _N = {"q": "attention.self.query", "k": "attention.self.key", "v": "attention.self.value",
+          "ao": "attention.output.dense", "ln1": "attention.output.LayerNorm",
+          "fc1": "intermediate.dense", "fc2": "output.dense", "ln2": "output.LayerNorm"}
+    _TYPE_EMB = "embeddings.token_type_embeddings.weight"   # None: no token-type table
+    _DROP_AFTER_ATTN_OUT = True    # BertSelfOutput: dropout(dense(ctx)) + residual
+    _HF_PREFIX = "bert."
+
     def __init__(self, config: TinyBertConfig = None, compute_dtype: str = "bf16", device=None):
         super().__init__()
         cfg = config or TinyBertConfig()
@@ -147,7 +157,8 @@ class TinyBertTower(ArenaModule):
 
     def load_hf_state_dict(self, sd):
         """Load a HF BertModel state dict (e.g. TinyBERT_General_4L_312D)."""
-        sd = {k[len("bert."):] if k.startswith("bert.") else k: v for k, v in sd.items()}
+        pre = self._HF_PREFIX
+        sd = {k[len(pre):] if k.startswith(pre) else k: v for k, v in sd.items()}
         return self.load_state_dict({k: v for k, v in sd.items() if k in self.state_dict()}, strict=False)
 
     def _wcopy(self):
@@ -166,8 +177,8 @@ class TinyBertTower(ArenaModule):
         return self.arena.view(name, wT)
 
     def _qkv(self, wT, i, bias=False, grad=False):
-        p = f"encoder.layer.{i}.attention.self."
-        names = [p + f"{n}.{'bias' if bias else 'weight'}" for n in ("query", "key", "value")]
+        p = self._LAYER.format(i)
+        names = [p + self._N[n] + (".bias" if bias else ".weight") for n in ("q", "k", "v")]
         o, n = self.arena.span(names)
         D = self.cfg.hidden
         buf = self.arena.grad if grad else wT
@@ -181,7 +192,7 @@ class TinyBertTower(ArenaModule):
         attention-output, LayerNorm and FFN work on the B CLS rows (its keys and
         values still cover every token), since the caller (VisionLanguageModule
         TextEncoder, :57-60) reads token 0 only."""
-        cfg = self.cfg
+        cfg, N = self.cfg, self._N
         D, Fd, H = cfg.hidden, cfg.ffn, cfg.heads
         dh = D // H
         dev = self.arena.data.device
@@ -189,19 +200,20 @@ class TinyBertTower(ArenaModule):
         B, Tn = input_ids.shape
         M = B * Tn
         ids = input_ids.contiguous().to(device=dev, dtype=torch.long)
-        tt = None if token_type_ids is None else token_type_ids.contiguous().to(device=dev, dtype=torch.long)
+        tt = None if token_type_ids is None or not self._TYPE_EMB else token_type_ids.contiguous().to(device=dev, dtype=torch.long)
         am = None if attention_mask is None else attention_mask.contiguous().to(device=dev, dtype=torch.long)
         wT = self._wcopy()
         A = self.arena.data
         p_h = cfg.hidden_dropout if training else 0.0
         p_a = cfg.attention_dropout if training else 0.0
+        p_o = p_h if self._DROP_AFTER_ATTN_OUT else 0.0
         self._seed = (self._seed * 6364136223846793005 + 1442695040888963407) % (2 ** 63)
         seed = self._seed
-        sv = {"B": B, "Tn": Tn, "ids": ids, "tt": tt, "seed": seed, "p_h": p_h, "p_a": p_a}
+        sv = {"B": B, "Tn": Tn, "ids": ids, "tt": tt, "seed": seed, "p_h": p_h, "p_a": p_a, "p_o": p_o}
         e = torch.empty(M, D, dtype=T, device=dev)
         ops.embed_fwd(ids, tt, self.arena.view("embeddings.word_embeddings.weight"),
                       self.arena.view("embeddings.position_embeddings.weight"),
-                      self.arena.view("embeddings.token_type_embeddings.weight"), e, M, Tn, D)
+                      self.arena.view(self._TYPE_EMB) if self._TYPE_EMB else None, e, M, Tn, D)
         h = torch.empty(M, D, dtype=T, device=dev)
         mu = torch.empty(M, device=dev)
         rs = torch.empty(M, device=dev)
@@ -212,10 +224,10 @@ class TinyBertTower(ArenaModule):
         layers = []
         scale = 1.0 / math.sqrt(dh)
         for i in range(cfg.layers):
-            p = f"encoder.layer.{i}."
+            p = self._LAYER.format(i)
             s_i = seed + 100 * (i + 1)
             if cls_only and i == cfg.layers - 1:
-                layers.append(self._last_layer_cls(h, wT, A, am, B, Tn, p, s_i, p_h, p_a, scale))
+                layers.append(self._last_layer_cls(h, wT, A, am, B, Tn, p, s_i, p_h, p_a, p_o, scale))
                 h = layers[-1]["h2"]
                 break
             qkv = torch.empty(M, 3 * D, dtype=T, device=dev)
@@ -224,28 +236,28 @@ class TinyBertTower(ArenaModule):
             P = torch.empty(B, H, Tn, Tn, device=dev)
             ops.attn_fwd(qkv, am, ctx, P, B, Tn, H, dh, scale, p=p_a, seed=s_i + 1)
             s1 = torch.empty(M, D, dtype=T, device=dev)
-            ops.linear_fwd(ctx, self._w(wT, p + "attention.output.dense.weight"),
-                           self.arena.view(p + "attention.output.dense.bias"), s1, M, D, D, mode=2,
-                           res=h, p=p_h, seed=s_i + 2)
+            ops.linear_fwd(ctx, self._w(wT, p + N["ao"] + ".weight"),
+                           self.arena.view(p + N["ao"] + ".bias"), s1, M, D, D, mode=2,
+                           res=h, p=p_o, seed=s_i + 2)
             h1 = torch.empty(M, D, dtype=T, device=dev)
             mu1 = torch.empty(M, device=dev)
             rs1 = torch.empty(M, device=dev)
-            ops.layernorm_fwd(s1, self.arena.view(p + "attention.output.LayerNorm.weight"),
-                              self.arena.view(p + "attention.output.LayerNorm.bias"), cfg.ln_eps, h1,
+            ops.layernorm_fwd(s1, self.arena.view(p + N["ln1"] + ".weight"),
+                              self.arena.view(p + N["ln1"] + ".bias"), cfg.ln_eps, h1,
                               mu1, rs1, M, D)
             u = torch.empty(M, Fd, dtype=T, device=dev)
             f = torch.empty(M, Fd, dtype=T, device=dev)
-            ops.linear_fwd(h1, self._w(wT, p + "intermediate.dense.weight"),
-                           self.arena.view(p + "intermediate.dense.bias"), f, M, Fd, D, mode=1, aux=u)
+            ops.linear_fwd(h1, self._w(wT, p + N["fc1"] + ".weight"),
+                           self.arena.view(p + N["fc1"] + ".bias"), f, M, Fd, D, mode=1, aux=u)
             s2 = torch.empty(M, D, dtype=T, device=dev)
-            ops.linear_fwd(f, self._w(wT, p + "output.dense.weight"),
-                           self.arena.view(p + "output.dense.bias"), s2, M, D, Fd, mode=2, res=h1,
+            ops.linear_fwd(f, self._w(wT, p + N["fc2"] + ".weight"),
+                           self.arena.view(p + N["fc2"] + ".bias"), s2, M, D, Fd, mode=2, res=h1,
                            p=p_h, seed=s_i + 3)
             h2 = torch.empty(M, D, dtype=T, device=dev)
             mu2 = torch.empty(M, device=dev)
             rs2 = torch.empty(M, device=dev)
-            ops.layernorm_fwd(s2, self.arena.view(p + "output.LayerNorm.weight"),
-                              self.arena.view(p + "output.LayerNorm.bias"), cfg.ln_eps, h2, mu2, rs2, M, D)
+            ops.layernorm_fwd(s2, self.arena.view(p + N["ln2"] + ".weight"),
+                              self.arena.view(p + N["ln2"] + ".bias"), cfg.ln_eps, h2, mu2, rs2, M, D)
             layers.append({"h": h, "qkv": qkv, "ctx": ctx, "P": P, "s1": s1, "mu1": mu1, "rs1": rs1,
                            "h1": h1, "u": u, "f": f, "s2": s2, "mu2": mu2, "rs2": rs2, "seed": s_i})
             h = h2
@@ -255,10 +267,10 @@ class TinyBertTower(ArenaModule):
         sv["cls_only"] = cls_only
         return h, sv
 
-    def _last_layer_cls(self, h, wT, A, am, B, Tn, p, s_i, p_h, p_a, scale):
+    def _last_layer_cls(self, h, wT, A, am, B, Tn, p, s_i, p_h, p_a, p_o, scale):
         """Last encoder layer for the CLS rows (row b*Tn of every [B*Tn] tensor,
         read in place through the GEMMs' leading dimensions)."""
-        cfg = self.cfg
+        cfg, N = self.cfg, self._N
         D, Fd, H = cfg.hidden, cfg.ffn, cfg.heads
         dh = D // H
         M = B * Tn
@@ -270,66 +282,66 @@ class TinyBertTower(ArenaModule):
         P = torch.empty(B, H, Tn, Tn, device=dev)
         ops.attn_fwd(qkv, am, ctx, P, B, Tn, H, dh, scale, p=p_a, seed=s_i + 1)
         s1 = torch.empty(B, D, dtype=T, device=dev)
-        ops.linear_fwd(ctx, self._w(wT, p + "attention.output.dense.weight"),
-                       self.arena.view(p + "attention.output.dense.bias"), s1, B, D, D, ldx=Tn * D, mode=2,
-                       res=h, ldr=Tn * D, p=p_h, seed=s_i + 2)
+        ops.linear_fwd(ctx, self._w(wT, p + N["ao"] + ".weight"),
+                       self.arena.view(p + N["ao"] + ".bias"), s1, B, D, D, ldx=Tn * D, mode=2,
+                       res=h, ldr=Tn * D, p=p_o, seed=s_i + 2)
         h1 = torch.empty(B, D, dtype=T, device=dev)
         mu1 = torch.empty(B, device=dev)
         rs1 = torch.empty(B, device=dev)
-        ops.layernorm_fwd(s1, self.arena.view(p + "attention.output.LayerNorm.weight"),
-                          self.arena.view(p + "attention.output.LayerNorm.bias"), cfg.ln_eps, h1, mu1, rs1, B, D)
+        ops.layernorm_fwd(s1, self.arena.view(p + N["ln1"] + ".weight"),
+                          self.arena.view(p + N["ln1"] + ".bias"), cfg.ln_eps, h1, mu1, rs1, B, D)
         u = torch.empty(B, Fd, dtype=T, device=dev)
         f = torch.empty(B, Fd, dtype=T, device=dev)
-        ops.linear_fwd(h1, self._w(wT, p + "intermediate.dense.weight"),
-                       self.arena.view(p + "intermediate.dense.bias"), f, B, Fd, D, mode=1, aux=u)
+        ops.linear_fwd(h1, self._w(wT, p + N["fc1"] + ".weight"),
+                       self.arena.view(p + N["fc1"] + ".bias"), f, B, Fd, D, mode=1, aux=u)
         s2 = torch.empty(B, D, dtype=T, device=dev)
-        ops.linear_fwd(f, self._w(wT, p + "output.dense.weight"), self.arena.view(p + "output.dense.bias"), s2,
+        ops.linear_fwd(f, self._w(wT, p + N["fc2"] + ".weight"), self.arena.view(p + N["fc2"] + ".bias"), s2,
                        B, D, Fd, mode=2, res=h1, p=p_h, seed=s_i + 3)
         h2 = torch.empty(B, D, dtype=T, device=dev)
         mu2 = torch.empty(B, device=dev)
         rs2 = torch.empty(B, device=dev)
-        ops.layernorm_fwd(s2, self.arena.view(p + "output.LayerNorm.weight"),
-                          self.arena.view(p + "output.LayerNorm.bias"), cfg.ln_eps, h2, mu2, rs2, B, D)
+        ops.layernorm_fwd(s2, self.arena.view(p + N["ln2"] + ".weight"),
+                          self.arena.view(p + N["ln2"] + ".bias"), cfg.ln_eps, h2, mu2, rs2, B, D)
         return {"h": h, "qkv": qkv, "ctx": ctx, "P": P, "s1": s1, "mu1": mu1, "rs1": rs1, "h1": h1, "u": u,
                 "f": f, "s2": s2, "mu2": mu2, "rs2": rs2, "h2": h2, "seed": s_i, "cls": True}
 
-    def _last_layer_cls_backward(self, Ls, dcls, wT, B, Tn, p_h, p_a, scale):
+    def _last_layer_cls_backward(self, Ls, dcls, wT, B, Tn, p_h, p_a, p_o, scale):
         """Backward of _last_layer_cls; returns the gradient of its input [B*Tn, D]."""
-        cfg = self.cfg
+        cfg, N = self.cfg, self._N
         D, Fd, H = cfg.hidden, cfg.ffn, cfg.heads
         dh = D // H
         M = B * Tn
         T, dev = self.tdtype, self.arena.data.device
         G = self.arena
         i = cfg.layers - 1
-        p = f"encoder.layer.{i}."
+        p = self._LAYER.format(i)
         s_i = Ls["seed"]
         dc = dcls.to(T).contiguous()
         ds2 = torch.empty(B, D, dtype=T, device=dev)
         dz = torch.empty(B, D, dtype=T, device=dev)
-        ops.layernorm_bwd(dc, Ls["s2"], Ls["mu2"], Ls["rs2"], self.arena.view(p + "output.LayerNorm.weight"),
-                          ds2, dz, G.gview(p + "output.LayerNorm.weight"), G.gview(p + "output.LayerNorm.bias"),
+        ops.layernorm_bwd(dc, Ls["s2"], Ls["mu2"], Ls["rs2"], self.arena.view(p + N["ln2"] + ".weight"),
+                          ds2, dz, G.gview(p + N["ln2"] + ".weight"), G.gview(p + N["ln2"] + ".bias"),
                           B, D, p_in=p_h, seed_in=s_i + 3)
-        ops.colsum(dz, G.gview(p + "output.dense.bias"), B, D)
-        ops.linear_wgrad(dz, Ls["f"], G.gview(p + "output.dense.weight"), B, D, Fd)
+        ops.colsum(dz, G.gview(p + N["fc2"] + ".bias"), B, D)
+        ops.linear_wgrad(dz, Ls["f"], G.gview(p + N["fc2"] + ".weight"), B, D, Fd)
         du = torch.empty(B, Fd, dtype=T, device=dev)
-        ops.linear_dgrad(dz, self._w(wT, p + "output.dense.weight"), du, B, Fd, D, mode=1, aux=Ls["u"])
-        ops.colsum(du, G.gview(p + "intermediate.dense.bias"), B, Fd)
-        ops.linear_wgrad(du, Ls["h1"], G.gview(p + "intermediate.dense.weight"), B, Fd, D)
+        ops.linear_dgrad(dz, self._w(wT, p + N["fc2"] + ".weight"), du, B, Fd, D, mode=1, aux=Ls["u"])
+        ops.colsum(du, G.gview(p + N["fc1"] + ".bias"), B, Fd)
+        ops.linear_wgrad(du, Ls["h1"], G.gview(p + N["fc1"] + ".weight"), B, Fd, D)
         dh1 = torch.empty(B, D, dtype=T, device=dev)
-        ops.linear_dgrad(du, self._w(wT, p + "intermediate.dense.weight"), dh1, B, D, Fd, addend=ds2)
+        ops.linear_dgrad(du, self._w(wT, p + N["fc1"] + ".weight"), dh1, B, D, Fd, addend=ds2)
         ds1 = torch.empty(B, D, dtype=T, device=dev)
         da = torch.empty(B, D, dtype=T, device=dev)
         ops.layernorm_bwd(dh1, Ls["s1"], Ls["mu1"], Ls["rs1"],
-                          self.arena.view(p + "attention.output.LayerNorm.weight"), ds1, da,
-                          G.gview(p + "attention.output.LayerNorm.weight"),
-                          G.gview(p + "attention.output.LayerNorm.bias"), B, D, p_in=p_h, seed_in=s_i + 2)
-        ops.colsum(da, G.gview(p + "attention.output.dense.bias"), B, D)
-        ops.linear_wgrad(da, Ls["ctx"], G.gview(p + "attention.output.dense.weight"), B, D, D, ldx=Tn * D)
+                          self.arena.view(p + N["ln1"] + ".weight"), ds1, da,
+                          G.gview(p + N["ln1"] + ".weight"),
+                          G.gview(p + N["ln1"] + ".bias"), B, D, p_in=p_o, seed_in=s_i + 2)
+        ops.colsum(da, G.gview(p + N["ao"] + ".bias"), B, D)
+        ops.linear_wgrad(da, Ls["ctx"], G.gview(p + N["ao"] + ".weight"), B, D, D, ldx=Tn * D)
         # only the CLS queries receive a context gradient; the residual gradient
         # ds1 reaches the CLS rows of the layer input
         dctx = torch.zeros(M, D, dtype=T, device=dev)
-        ops.linear_dgrad(da, self._w(wT, p + "attention.output.dense.weight"), dctx, B, D, D, lddx=Tn * D)
+        ops.linear_dgrad(da, self._w(wT, p + N["ao"] + ".weight"), dctx, B, D, D, lddx=Tn * D)
         dqkv = torch.empty(M, 3 * D, dtype=T, device=dev)
         ops.attn_bwd(Ls["qkv"], Ls["P"], dctx, dqkv, B, Tn, H, dh, scale, p=p_a, seed=s_i + 1)
         ops.colsum(dqkv, self._qkv(None, i, bias=True, grad=True), M, 3 * D)
@@ -344,7 +356,7 @@ class TinyBertTower(ArenaModule):
     def run_backward(self, sv, dcls):
         """dcls: [B, D] gradient of the CLS hidden states (any dtype).  Zeroes and
         fills the grad arena (pooler gradient stays zero: unused, as in the reference)."""
-        cfg = self.cfg
+        cfg, N = self.cfg, self._N
         D, Fd, H = cfg.hidden, cfg.ffn, cfg.heads
         dh = D // H
         dev = self.arena.data.device
@@ -354,45 +366,45 @@ class TinyBertTower(ArenaModule):
         wT = sv["wT"]
         G = self.arena
         G.grad.zero_()
-        p_h, p_a = sv["p_h"], sv["p_a"]
+        p_h, p_a, p_o = sv["p_h"], sv["p_a"], sv["p_o"]
         scale = 1.0 / math.sqrt(dh)
         top = cfg.layers - 1
         if sv.get("cls_only"):
-            dh_ = self._last_layer_cls_backward(sv["layers"][top], dcls, wT, B, Tn, p_h, p_a, scale)
+            dh_ = self._last_layer_cls_backward(sv["layers"][top], dcls, wT, B, Tn, p_h, p_a, p_o, scale)
             top -= 1
         else:
             dh_ = torch.zeros(M, D, dtype=T, device=dev)
             dc = dcls.to(T).contiguous()
             ops.scatter_rows(dc, dh_, B, D, D, Tn * D)
         for i in range(top, -1, -1):
-            p = f"encoder.layer.{i}."
+            p = self._LAYER.format(i)
             Ls = sv["layers"][i]
             s_i = Ls["seed"]
             # output LayerNorm: ds2 (residual) and dz = ds2 * dropout mask
             ds2 = torch.empty(M, D, dtype=T, device=dev)
             dz = torch.empty(M, D, dtype=T, device=dev)
-            ops.layernorm_bwd(dh_, Ls["s2"], Ls["mu2"], Ls["rs2"], self.arena.view(p + "output.LayerNorm.weight"),
-                              ds2, dz, G.gview(p + "output.LayerNorm.weight"), G.gview(p + "output.LayerNorm.bias"),
+            ops.layernorm_bwd(dh_, Ls["s2"], Ls["mu2"], Ls["rs2"], self.arena.view(p + N["ln2"] + ".weight"),
+                              ds2, dz, G.gview(p + N["ln2"] + ".weight"), G.gview(p + N["ln2"] + ".bias"),
                               M, D, p_in=p_h, seed_in=s_i + 3)
-            ops.colsum(dz, G.gview(p + "output.dense.bias"), M, D)
-            ops.linear_wgrad(dz, Ls["f"], G.gview(p + "output.dense.weight"), M, D, Fd)
+            ops.colsum(dz, G.gview(p + N["fc2"] + ".bias"), M, D)
+            ops.linear_wgrad(dz, Ls["f"], G.gview(p + N["fc2"] + ".weight"), M, D, Fd)
             du = torch.empty(M, Fd, dtype=T, device=dev)
-            ops.linear_dgrad(dz, self._w(wT, p + "output.dense.weight"), du, M, Fd, D, mode=1, aux=Ls["u"])
-            ops.colsum(du, G.gview(p + "intermediate.dense.bias"), M, Fd)
-            ops.linear_wgrad(du, Ls["h1"], G.gview(p + "intermediate.dense.weight"), M, Fd, D)
+            ops.linear_dgrad(dz, self._w(wT, p + N["fc2"] + ".weight"), du, M, Fd, D, mode=1, aux=Ls["u"])
+            ops.colsum(du, G.gview(p + N["fc1"] + ".bias"), M, Fd)
+            ops.linear_wgrad(du, Ls["h1"], G.gview(p + N["fc1"] + ".weight"), M, Fd, D)
             dh1 = torch.empty(M, D, dtype=T, device=dev)
-            ops.linear_dgrad(du, self._w(wT, p + "intermediate.dense.weight"), dh1, M, D, Fd, addend=ds2)
+            ops.linear_dgrad(du, self._w(wT, p + N["fc1"] + ".weight"), dh1, M, D, Fd, addend=ds2)
             # attention output LayerNorm
             ds1 = torch.empty(M, D, dtype=T, device=dev)
             da = torch.empty(M, D, dtype=T, device=dev)
             ops.layernorm_bwd(dh1, Ls["s1"], Ls["mu1"], Ls["rs1"],
-                              self.arena.view(p + "attention.output.LayerNorm.weight"), ds1, da,
-                              G.gview(p + "attention.output.LayerNorm.weight"),
-                              G.gview(p + "attention.output.LayerNorm.bias"), M, D, p_in=p_h, seed_in=s_i + 2)
-            ops.colsum(da, G.gview(p + "attention.output.dense.bias"), M, D)
-            ops.linear_wgrad(da, Ls["ctx"], G.gview(p + "attention.output.dense.weight"), M, D, D)
+                              self.arena.view(p + N["ln1"] + ".weight"), ds1, da,
+                              G.gview(p + N["ln1"] + ".weight"),
+                              G.gview(p + N["ln1"] + ".bias"), M, D, p_in=p_o, seed_in=s_i + 2)
+            ops.colsum(da, G.gview(p + N["ao"] + ".bias"), M, D)
+            ops.linear_wgrad(da, Ls["ctx"], G.gview(p + N["ao"] + ".weight"), M, D, D)
             dctx = torch.empty(M, D, dtype=T, device=dev)
-            ops.linear_dgrad(da, self._w(wT, p + "attention.output.dense.weight"), dctx, M, D, D)
+            ops.linear_dgrad(da, self._w(wT, p + N["ao"] + ".weight"), dctx, M, D, D)
             dqkv = torch.empty(M, 3 * D, dtype=T, device=dev)
             ops.attn_bwd(Ls["qkv"], Ls["P"], dctx, dqkv, B, Tn, H, dh, scale, p=p_a, seed=s_i + 1)
             ops.colsum(dqkv, self._qkv(None, i, bias=True, grad=True), M, 3 * D)
@@ -407,7 +419,7 @@ class TinyBertTower(ArenaModule):
                           M, D, p_out=p_h, seed_out=sv["seed"] + 1)
         ops.embed_bwd(sv["ids"], sv["tt"], de, G.gview("embeddings.word_embeddings.weight"),
                       G.gview("embeddings.position_embeddings.weight"),
-                      G.gview("embeddings.token_type_embeddings.weight"), M, Tn, D)
+                      G.gview(self._TYPE_EMB) if self._TYPE_EMB else None, M, Tn, D)
 
     def grads_for_autograd(self, existing=None):
         out = super().grads_for_autograd()
