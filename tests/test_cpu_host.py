@@ -58,6 +58,32 @@ def test_every_declaration_cites_the_reference():
         assert re.search(r"\w+\.py:\d+", sec.split("*/")[0]), sec[:80]
 
 
+def test_every_kernel_switch_is_in_the_design_table():
+    """Every `#ifndef VLP_...` compile-time switch of csrc/ has a row in DESIGN.md's
+    "Kernel variants" table and every constant the table names exists: an
+    undocumented (or wrong-result timing) switch cannot creep back in."""
+    import glob
+    import re
+    defined = set()
+    for path in glob.glob(os.path.join(PKG, "csrc", "*.hip")) + glob.glob(os.path.join(PKG, "csrc", "*.h")):
+        defined |= set(re.findall(r"^\s*#\s*ifndef\s+(VLP_\w+)", open(path).read(), re.M))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design.split("**Kernel variants.**", 1)[1]
+    rows = []
+    for line in section.splitlines():
+        if line.startswith("|"):
+            rows.append(line)
+        elif rows:
+            break          # the table ends at the first line after it that is not a row
+    assert len(rows) > 2, "Kernel variants table not found in DESIGN.md"
+    # a row's first cell names its constant(s) in backticks
+    documented = {n for row in rows[2:] for n in re.findall(r"`(VLP_\w+)`", row.split("|")[1])}
+    assert defined, "no #ifndef VLP_ switch found under csrc/"
+    assert defined == documented, (
+        f"switches without a DESIGN.md row: {sorted(defined - documented)}; "
+        f"rows without a switch: {sorted(documented - defined)}")
+
+
 def test_missing_library_fails_loudly(tmp_path):
     code = ("import sys; sys.path[:0]=[%r, %r]\n"
             "try:\n    from vlp_amd import _lib; _lib.lib()\nexcept ImportError as e:\n"

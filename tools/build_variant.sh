@@ -1,5 +1,5 @@
 # build a variant of libvlp_hip.so with extra -D flags into build_exp/<name>/libvlp_hip.so
-#   tools/build_variant.sh NAME "-DVLP_BIG_SCHED=1 ..." [object ...]
+#   tools/build_variant.sh NAME "-DVLP_PP_PRIO=0 ..." [object ...]
 # with object names given (e.g. conv_ops), only those are recompiled with the
 # flags; the others are linked from the product build (csrc/build/*.o)
 set -e

@@ -188,7 +188,7 @@ static int gemm_lin(int M, int N, int K, int ksplit, const LA& la, const LB& lb,
     // VLP_LIN_PP: 0 off, 1 same-layout GEMMs only, 2 (default) also the data gradients
     // (NesT step +2.6 % and +0.7 %)
     constexpr int lin_pp = 2;   // linear GEMMs on the ping-pong kernel: same-layout and data gradients (measured)
-    if (lin_pp && gemm_variant() >= 5 && M >= 256 && N >= 256 && K >= 256 && K % 64 == 0) {
+    if (lin_pp && M >= 256 && N >= 256 && K >= 256 && K % 64 == 0) {
       if constexpr (LA::kKContig == LB::kKContig) return gemm_big_auto(M, N, K, ksplit, la, lb, ep, st);
       // data gradients (K-contig dy x MN-contig W)
       else if (lin_pp >= 2) return launch_gemm_pp<256, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
@@ -201,7 +201,7 @@ static int gemm_lin(int M, int N, int K, int ksplit, const LA& la, const LB& lb,
     // and for N <= 128; loses on the K = 96, N >= 288 level-0 qkv / fc1: 674 -> 780,
     // 1123 -> 1324, which keep the one-tile ring)
     if constexpr (LA::kKContig && LB::kKContig) {
-      if (VLP_LIN_SHORTK && gemm_variant() >= 5 && M >= 65536 && N >= 96 && (K >= 192 || N <= 128))
+      if (VLP_LIN_SHORTK && M >= 65536 && N >= 96 && (K >= 192 || N <= 128))
         return gemm_big_auto(M, N, K, ksplit, la, lb, ep, st);
     }
   }
@@ -952,8 +952,8 @@ VLP_EXPORT int vlp_linear_wgrad(int dtype, int M, int Nout, int Kin, const void*
   constexpr int rows_per_split = 1024;
   int tiles = ((Nout + 127) / 128) * ((Kin + 127) / 128);
   int ksplit = (512 + tiles - 1) / tiles;
-  int maxsplit = (M + rows_per_split - 1) / rows_per_split;
-  if (ksplit > maxsplit) ksplit = maxsplit;
+  int max_split = (M + rows_per_split - 1) / rows_per_split;
+  if (ksplit > max_split) ksplit = max_split;
   EpiAtomic ep{nullptr, nullptr, dw, Kin, 1.0f};
   if (dtype == VLP_BF16) {
     MNMat<bf16> la{(const bf16*)dy, lddy, Nout, M};
@@ -971,8 +971,8 @@ VLP_EXPORT int vlp_linear_wgrad(int dtype, int M, int Nout, int Kin, const void*
 static int linw_splits(int M, int Nout, int Kin) {
   const int tiles = ((Nout + 127) / 128) * ((Kin + 127) / 128);
   int ks = (512 + tiles - 1) / tiles;
-  const int maxsplit = (M + 255) / 256;
-  if (ks > maxsplit) ks = maxsplit;
+  const int max_split = (M + 255) / 256;
+  if (ks > max_split) ks = max_split;
   return ks;
 }
 static int linw_splits_pp(int M, int Nout, int Kin) {
@@ -982,7 +982,7 @@ static int linw_splits_pp(int M, int Nout, int Kin) {
   return k2;
 }
 static bool linw_use_pp(int M, int Nout, int Kin) {
-  return gemm_variant() >= 5 && Nout >= 256 && Kin >= 256 && M >= 16384 && M % 64 == 0;
+  return Nout >= 256 && Kin >= 256 && M >= 16384 && M % 64 == 0;
 }
 // fp32 elements of the split-K workspace vlp_linear_wgrad_ws uses at its full split
 // count for this shape (a smaller workspace trims the splits)

@@ -57,8 +57,8 @@ __device__ __forceinline__ uint4 xform_chunk(uint4 v, const float* sc, const flo
 }
 
 // Loaders carry two protocols (gemm.h): fixed/load (register staging: fp32
-// parity mode, BN-on-load) and start/next (incremental direct-to-LDS, bf16).
-// The direct path requires the channel count to be a multiple of the K-step
+// parity mode, BN-on-load) and the buffer protocol (LDS-DMA kernels, bf16).
+// The buffer path requires the channel count to be a multiple of the K-step
 // (64), so a K-step never straddles a filter tap and (kh, kw, channel offset)
 // are wave-uniform scalars; every ResNet34 conv except the stem satisfies it
 // (the stem has its own loaders).
@@ -82,7 +82,6 @@ __device__ __forceinline__ int conv_kperm(int k, int K, int taps, int nch) {
 template <typename T, bool XF>
 struct ConvFwdA {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = !XF;
   static constexpr bool kKPerm = VLP_KPERM && std::is_same<T, bf16>::value && !XF;
   __device__ int kperm(int k) const {
     return g.C % 64 ? k : conv_kperm(k, g.K, g.KH * g.KW, g.C >> 6);
@@ -114,26 +113,7 @@ struct ConvFwdA {
     if constexpr (XF) v = xform_chunk<T>(v, sc, sh, ci);
     return v;
   }
-  struct DState { long long off; int hi0, wi0; bool ok; };
-  __device__ DState start(int m, int koff, int) const {
-    State f = fixed(m);
-    DState d;
-    d.ok = f.ok; d.hi0 = f.hi0; d.wi0 = f.wi0;
-    d.off = (long long)(f.base - x) + ((long long)f.hi0 * g.W + f.wi0) * g.C + koff;
-    return d;
-  }
-  struct Step { long long delta; int kh, kw; bool kv; };   // K-step-uniform tap
-  __device__ Step step(int k0) const {
-    const int tap = fdiv(k0, g.fd_c), ci0 = k0 - tap * g.C;
-    const int kh = fdiv(tap, g.fd_kw), kw = tap - kh * g.KW;
-    return Step{((long long)kh * g.W + kw) * g.C + ci0, kh, kw, k0 < g.K};
-  }
-  __device__ const void* next(DState& d, const Step& s) const {
-    const bool v = d.ok & s.kv & ((unsigned)(d.hi0 + s.kh) < (unsigned)g.H) &
-                   ((unsigned)(d.wi0 + s.kw) < (unsigned)g.W);
-    return v ? (const void*)(x + d.off + s.delta) : zero_page();
-  }
-  // buffer protocol (gemm_bk / gemm_big): the chunk's row is fixed, so the
+  // buffer protocol: the chunk's row is fixed, so the
   // validity of all KH*KW taps is one bit mask computed once; a K-step is
   // (tap, channel offset) -> one scalar byte delta
   static constexpr bool kBuf = !XF;
@@ -174,10 +154,9 @@ struct ConvFwdABn : ConvFwdA<bf16, false> {
   }
 };
 // the same operand through register staging only (per-chunk filter tap): for
-// channel counts the one-tap-per-K-step LDS-DMA / direct loaders cannot take
+// channel counts the one-tap-per-K-step LDS-DMA loaders cannot take
 template <typename T>
 struct ConvFwdAReg : ConvFwdA<T, false> {
-  static constexpr bool kDirect = false;
   static constexpr bool kBuf = false;
 };
 
@@ -185,7 +164,6 @@ struct ConvFwdAReg : ConvFwdA<T, false> {
 template <typename T>
 struct ConvDgradA {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = true;
   // the chunk-major order measured slower here (layer 3/4 +7-8 % per launch, r4d): tap-major kept
   static constexpr bool kKPerm = false;
   __device__ int kperm(int k) const { return k; }
@@ -220,26 +198,7 @@ struct ConvDgradA {
     if (ho >= g.Ho || wo >= g.Wo) return zero4();
     return ldg16(s.base + ((size_t)ho * g.Wo + wo) * g.Co + co);
   }
-  struct DState { long long off; int hp, wp; bool ok; };
-  __device__ DState start(int m, int koff, int) const {
-    State f = fixed(m);
-    DState d;
-    d.ok = f.ok; d.hp = f.hp; d.wp = f.wp;
-    d.off = (long long)(f.base - dy) + ((long long)f.hp * g.Wo + f.wp) * g.Co + koff;
-    return d;
-  }
-  struct Step { long long delta; int kh, kw; bool kv; };
-  __device__ Step step(int k0) const {   // stride-1 only (S=2: ConvDgradS2A)
-    const int tap = fdiv(k0, g.fd_co), co0 = k0 - tap * g.Co;
-    const int kh = fdiv(tap, g.fd_kw), kw = tap - kh * g.KW;
-    return Step{co0 - ((long long)kh * g.Wo + kw) * g.Co, kh, kw, k0 < g.K};
-  }
-  __device__ const void* next(DState& d, const Step& s) const {
-    const bool v = d.ok & s.kv & ((unsigned)(d.hp - s.kh) < (unsigned)g.Ho) &
-                   ((unsigned)(d.wp - s.kw) < (unsigned)g.Wo);
-    return v ? (const void*)(dy + d.off + s.delta) : zero_page();
-  }
-  // buffer protocol (stride 1): per-chunk tap mask, scalar byte delta per K-step
+  // buffer protocol (stride 1 only; S = 2: ConvDgradS2A): per-chunk tap mask, scalar byte delta per K-step
   static constexpr bool kBuf = true;
   struct BState { unsigned base; unsigned mask; };
   struct BStep { unsigned delta; unsigned tap; };
@@ -295,7 +254,6 @@ static S2Class make_s2class(const ConvGeom& g, int ph, int pw) {
 template <typename T>
 struct ConvDgradS2A {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = true;
   struct State { const T* base; int hb, wb; bool ok; };   // hb = (h + P - kh0) / 2
   ConvGeom g; S2Class c; const T* dy; int Mc, Kc;
   int Kc1 = 1 << 30; long long dd_off = 0;                // downsample segment (buffer protocol only)
@@ -321,25 +279,6 @@ struct ConvDgradS2A {
     int ho = s.hb - a, wo = s.wb - b;
     if ((unsigned)ho >= (unsigned)g.Ho || (unsigned)wo >= (unsigned)g.Wo) return zero4();
     return ldg16(s.base + ((size_t)ho * g.Wo + wo) * g.Co + co);
-  }
-  struct DState { long long off; int hb, wb; bool ok; };
-  __device__ DState start(int m, int koff, int) const {
-    State f = fixed(m);
-    DState d;
-    d.ok = f.ok; d.hb = f.hb; d.wb = f.wb;
-    d.off = (long long)(f.base - dy) + ((long long)f.hb * g.Wo + f.wb) * g.Co + koff;
-    return d;
-  }
-  struct Step { long long delta; int a, b; bool kv; };
-  __device__ Step step(int k0) const {
-    const int tap = fdiv(k0, g.fd_co), co0 = k0 - tap * g.Co;
-    const int a = fdiv(tap, c.fd_ntw), b = tap - a * c.ntw;
-    return Step{co0 - ((long long)a * g.Wo + b) * g.Co, a, b, k0 < Kc};
-  }
-  __device__ const void* next(DState& d, const Step& s) const {
-    const bool v = d.ok & s.kv & ((unsigned)(d.hb - s.a) < (unsigned)g.Ho) &
-                   ((unsigned)(d.wb - s.b) < (unsigned)g.Wo);
-    return v ? (const void*)(dy + d.off + s.delta) : zero_page();
   }
   // buffer protocol: tap (a, b) of the class -> bit a*ntw + b
   static constexpr bool kBuf = true;
@@ -411,7 +350,6 @@ struct EpiS2Remap {
 template <typename T>
 struct WtS2B {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = true;
   struct State { const T* p; bool ok; };
   const T* wt; ConvGeom g; S2Class c; int Kc;
   int Kc1 = 1 << 30; long long wd_off = 0;                // downsample segment (buffer protocol only)
@@ -425,20 +363,6 @@ struct WtS2B {
     int a = fdiv(tap, c.fd_ntw);
     int b = tap - a * c.ntw;
     return ldg16(s.p + ((size_t)(c.kh0 + 2 * a) * g.KW + c.kw0 + 2 * b) * g.Co + co);
-  }
-  struct DState { const T* p; bool ok; };
-  __device__ DState start(int ci, int koff, int) const {
-    State f = fixed(ci);
-    return DState{f.p + koff, f.ok};
-  }
-  struct Step { long long delta; bool kv; };
-  __device__ Step step(int k0) const {
-    const int tap = fdiv(k0, g.fd_co), co0 = k0 - tap * g.Co;
-    const int a = fdiv(tap, c.fd_ntw), b = tap - a * c.ntw;
-    return Step{((long long)(c.kh0 + 2 * a) * g.KW + c.kw0 + 2 * b) * g.Co + co0, k0 < Kc};
-  }
-  __device__ const void* next(DState& d, const Step& s) const {
-    return (d.ok & s.kv) ? (const void*)(d.p + s.delta) : zero_page();
   }
   // buffer protocol (Kc is a multiple of the K-step: no per-chunk k check)
   static constexpr bool kBuf = true;
@@ -471,7 +395,7 @@ struct WtS2B {
 };
 
 // ---- weight-gradient B operand: input patches, MN-contiguous over (kh,kw,ci) ----
-// The reduction runs over output pixels; the direct path walks each chunk's
+// The reduction runs over output pixels; the buffer path walks each chunk's
 // pixel (n, ho, wo) incrementally, BK pixels per K-step (constant carries).
 struct PixStep {
   int dwo, dho;          // BK = dho*Wo + dwo
@@ -482,7 +406,6 @@ struct PixStep {
 template <typename T, bool XF>
 struct ConvWgradB {
   static constexpr bool kKContig = false;
-  static constexpr bool kDirect = !XF;
   struct State { int kh, kw, ci; bool ok; };
   ConvGeom g; const T* x; const float* sc; const float* sh; int Kcols; PixStep ps;
   __device__ State fixed(int col) const {
@@ -507,53 +430,10 @@ struct ConvWgradB {
     if constexpr (XF) v = xform_chunk<T>(v, sc, sh, s.ci);
     return v;
   }
-  // direct staging (GStagerN, MN-contig): one output-pixel walk per thread
-  // (RState, 32-bit element offsets; x < 2^31 elements is checked on the
-  // host) combined with a fixed (tap, channel) offset per chunk column.
-  struct RState { int poff, ho, wo, mm; };     // poff = ((n*H + ho*S)*W + wo*S)*C
-  struct CState { int colofs, khp, kwp; bool ok; };
-  __device__ void locate(RState& r) const {
-    const int mm = r.mm < g.M ? r.mm : 0;
-    const int n = fdiv(mm, g.fd_howo);
-    const int rr = mm - n * g.Ho * g.Wo;
-    r.ho = fdiv(rr, g.fd_wo);
-    r.wo = rr - r.ho * g.Wo;
-    r.poff = ((n * g.H + r.ho * g.S) * g.W + r.wo * g.S) * g.C;
-  }
-  __device__ RState rstart(int k, int kb) const {
-    RState r;
-    r.mm = kb + k;
-    locate(r);
-    return r;
-  }
-  __device__ CState cstart(int col) const {
-    const State f = fixed(col);
-    return CState{((f.kh - g.P) * g.W + (f.kw - g.P)) * g.C + f.ci, f.kh - g.P, f.kw - g.P, f.ok};
-  }
-  __device__ const void* addr(const RState& r, const CState& c) const {
-    const int hi = r.ho * g.S + c.khp, wi = r.wo * g.S + c.kwp;
-    const bool v = c.ok & (r.mm < g.M) & ((unsigned)hi < (unsigned)g.H) & ((unsigned)wi < (unsigned)g.W);
-    return v ? (const void*)(x + (r.poff + c.colofs)) : zero_page();
-  }
-  __device__ void radvance(RState& r) const {
-    r.mm += Elem<T>::BK;
-    if (ps.small) {   // tiny images (Ho*Wo <= BK): recompute
-      locate(r);
-      return;
-    }
-    r.wo += ps.dwo;
-    r.ho += ps.dho;
-    r.poff += ps.dpoff;
-    const bool cw = r.wo >= g.Wo;
-    r.wo = cw ? r.wo - g.Wo : r.wo;
-    r.ho = cw ? r.ho + 1 : r.ho;
-    r.poff = cw ? r.poff + ps.carry_w : r.poff;
-    const bool ch = r.ho >= g.Ho;
-    r.ho = ch ? r.ho - g.Ho : r.ho;
-    r.poff = ch ? r.poff + ps.carry_h : r.poff;
-  }
-  // buffer protocol: per pixel row a KH*KW tap-validity mask (recomputed as
-  // the row walks), per chunk column a fixed byte offset and tap index
+  // buffer protocol: one output-pixel walk per thread (BRow, 32-bit byte
+  // offsets; the operand size is checked on the host) with a KH*KW tap-validity
+  // mask (recomputed as the row walks), per chunk column a fixed byte offset and
+  // tap index
   static constexpr bool kBuf = !XF;
   struct BRow { int poff, hs, ws, mm; unsigned tmask; };   // poff: bytes of (n, ho*S, wo*S)
   struct BCol { unsigned ofs, tap; };
@@ -595,7 +475,7 @@ struct ConvWgradB {
   }
   __device__ void bradvance(BRow& r) const {
     r.mm += Elem<T>::BK;
-    if (ps.small) {
+    if (ps.small) {   // tiny images (Ho*Wo <= BK): recompute
       blocate(r);
       return;
     }
@@ -633,7 +513,6 @@ struct StemGeom {
 template <typename T>
 struct StemA {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = true;
   struct State { const T* base; bool ok; };
   StemGeom g; const T* xp;
   __device__ State fixed(int m) const {
@@ -652,16 +531,6 @@ struct StemA {
     if (!s.ok || kh >= 7) return zero4();
     return ldg16(s.base + ((size_t)kh * g.Wp + kw) * 4);
   }
-  struct DState { const T* p; int khc; bool ok; };
-  __device__ DState start(int m, int koff, int) const {
-    State f = fixed(m);
-    return DState{f.base + ((size_t)(koff >> 5) * g.Wp + ((koff & 31) >> 2)) * 4, koff >> 5, f.ok};
-  }
-  struct Step { int kh; long long delta; };
-  __device__ Step step(int k0) const { return Step{k0 >> 5, (long long)(k0 >> 5) * g.Wp * 4}; }
-  __device__ const void* next(DState& d, const Step& s) const {
-    return (d.ok & (s.kh + d.khc < 7)) ? (const void*)(d.p + s.delta) : zero_page();
-  }
   // buffer protocol: a chunk is valid while kh = k0/32 + its own kh stays < 7
   static constexpr bool kBuf = true;
   struct BState { unsigned base; int khlim; };
@@ -678,7 +547,6 @@ struct StemA {
 template <typename T>
 struct StemWgradB {
   static constexpr bool kKContig = false;
-  static constexpr bool kDirect = true;
   struct State { int off; bool ok; };
   StemGeom g; const T* xp;
   __device__ State fixed(int col) const {
@@ -693,34 +561,8 @@ struct StemWgradB {
     int wo = r - ho * g.Wo;
     return ldg16(xp + (((size_t)n * g.Hp + 2 * ho) * g.Wp + 2 * wo) * 4 + s.off);
   }
-  struct RState { int poff, mm; };   // pixel (n, 2ho, 2wo) of the padded image, x 4 channels
-  struct CState { int off; bool ok; };
-  __device__ RState rstart(int k, int kb) const {
-    RState r;
-    r.mm = kb + k;
-    locate(r);
-    return r;
-  }
-  __device__ void locate(RState& r) const {
-    const int m = r.mm < g.M ? r.mm : 0;
-    const int n = fdiv(m, g.fd_howo);
-    const int rr = m - n * g.Ho * g.Wo;
-    const int ho = fdiv(rr, g.fd_wo);
-    const int wo = rr - ho * g.Wo;
-    r.poff = ((n * g.Hp + 2 * ho) * g.Wp + 2 * wo) * 4;
-  }
-  __device__ CState cstart(int col) const {
-    const State f = fixed(col);
-    return CState{f.off, f.ok};
-  }
-  __device__ const void* addr(const RState& r, const CState& c) const {
-    return (c.ok & (r.mm < g.M)) ? (const void*)(xp + (r.poff + c.off)) : zero_page();
-  }
-  __device__ void radvance(RState& r) const {
-    r.mm += Elem<T>::BK;
-    locate(r);
-  }
   // buffer protocol: incremental pixel walk over (n, ho, wo) in the padded image
+  // (pixel (n, 2ho, 2wo), x 4 channels)
   static constexpr bool kBuf = true;
   PixStep ps;   // deltas in padded-image elements (make_stem_pixstep)
   struct BRow { int poff, ho, wo, mm; };
@@ -787,7 +629,6 @@ static PixStep make_stem_pixstep(const StemGeom& g, int BK) {
 template <typename T>
 struct Stem1A {
   static constexpr bool kKContig = true;
-  static constexpr bool kDirect = false;
   Stem1Geom g; const T* xs;
   struct State { const T* base; bool ok; };
   __device__ size_t pix(int m) const {   // element offset of (copy, n, 2ho, 2wo - 2s)
@@ -824,7 +665,6 @@ struct Stem1A {
 template <typename T>
 struct Stem1WgradB {   // B(n = kh*8 + kw, k = pixel m), MN-contiguous chunks of 8 (4) kw
   static constexpr bool kKContig = false;
-  static constexpr bool kDirect = false;
   Stem1Geom g; const T* xs;
   struct State { int off; bool ok; };
   __device__ State fixed(int col) const { return State{(col >> 3) * g.Wp1 + (col & 7), (col >> 3) < 7}; }
@@ -913,7 +753,7 @@ struct EpiConvFwd {
     s1 = v;
     s2 = v * v;
   }
-  // staged form (multi-stage kernel): value() -> LDS tile -> 16-B row stores
+  // staged form (LDS-DMA kernels' ms_epilogue): value() -> LDS tile -> 16-B row stores
   static constexpr bool kStage = true;
   __device__ v4f value(int, int, v4f v, v4f& s1, v4f& s2) const {
     s1 = v;
@@ -1238,35 +1078,33 @@ template <typename T, class LA, class LB, class EP>
 static int gemm_s2(int M, int N, int K, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
   if constexpr (use_bk<T, LA, LB>()) {
     // 256x64 on the two-tiles-in-flight engine: +3 % over the one-tile ring
-    constexpr int s2v = 1;
-    if (N <= 64 && s2v == 1) return launch_gemm_big<256, 64, 4, 1>(M, N, K, 1, la, lb, ep, st);
-    if (N <= 64 && s2v == 2) return launch_gemm_big<128, 64, 2, 1>(M, N, K, 1, la, lb, ep, st);
+    if (N <= 64) return launch_gemm_big<256, 64, 4, 1>(M, N, K, 1, la, lb, ep, st);
   }
   return gemm_auto<T>(M, N, K, 1, la, lb, ep, st);
 }
 // weight-gradient GEMMs: rows = Co, cols = KH*KW*C, reduction = pixels.
-//  Co = 64 (stem, layer1): 64 x 128 tiles, split-K chosen by the launcher to
-//    fill whole rounds of resident workgroups (ksplit = -2048: >= 2048 pixels)
-//  Co >= 128: ~1024 workgroups, >= 4096 pixels each, splits in multiples of 8
-//    so each XCD owns whole splits (GemmShape::xsplit); measured faster than
-//    the slot-balanced split for these shapes (r1: 21.1 vs 26.1 ms per step)
+//  Co = 64 (stem, layer1): split-K chosen by the launcher to fill whole rounds
+//    of resident workgroups (ksplit = -2048: >= 2048 pixels per split)
+//  Co >= 128, buffer-protocol loaders: large tiles, one workgroup per CU, the
+//    same slot-balanced split
+//  Co >= 128 on the register-staged kernel (fp32 parity mode, BN-on-load):
+//    ~1024 workgroups of 128 x 128 tiles, >= 4096 pixels each, split counts of
+//    8 or more rounded up to a multiple of 8
 template <typename T, class LA, class LB, class EP>
 static int gemm_wgrad(int M, int N, int K, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
   if (M <= 64) return gemm_short<T>(M, N, K, -2048, la, lb, ep, st);
-  if constexpr (use_bk<T, LA, LB>()) {   // large tiles, one workgroup per CU: slot-balanced split
-    constexpr int mink5 = 2048;
-    if (gemm_variant() >= 5) return gemm_conv_wide<T>(M, N, K, -mink5, la, lb, ep, st);
+  if constexpr (use_bk<T, LA, LB>()) {
+    return gemm_conv_wide<T>(M, N, K, -2048, la, lb, ep, st);
+  } else {
+    constexpr int target = 1024;
+    constexpr int mink = 4096;
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    int ksplit = (target + tiles - 1) / tiles;
+    const int max_split = (K + mink - 1) / mink;
+    if (ksplit > max_split) ksplit = max_split;
+    if (ksplit >= 8) ksplit = (ksplit + 7) / 8 * 8;
+    return gemm_wide<T>(M, N, K, ksplit, la, lb, ep, st);
   }
-  constexpr int balanced = 0;
-  if (balanced) return gemm_wide<T>(M, N, K, -balanced, la, lb, ep, st);
-  constexpr int target = 1024;
-  constexpr int mink = 4096;
-  const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-  int ksplit = (target + tiles - 1) / tiles;
-  const int maxsplit = (K + mink - 1) / mink;
-  if (ksplit > maxsplit) ksplit = maxsplit;
-  if (ksplit >= 8) ksplit = (ksplit + 7) / 8 * 8;
-  return gemm_wide<T>(M, N, K, ksplit, la, lb, ep, st);
 }
 
 // ---------------- row-streaming 3x3 conv, 64 -> 64 channels (layer1) ----------------
@@ -1295,9 +1133,6 @@ constexpr int kRcXtab = kRcTail + 2048;          // input-transform table: (scal
 constexpr int kRcLds = kRcXtab + 768;
 static_assert(kRcLds <= 160 * 1024, "rows kernel LDS map");
 
-#ifndef VLP_ACT_NT
-#define VLP_ACT_NT 0   // non-temporal stores of the transformed input rows
-#endif
 // Input transforms (XF), applied once per input row, in place in the ring right
 // after the row lands (padding rows stay zero), the result also written to
 // xin.out (the operand the weight gradient reads):
@@ -1466,13 +1301,7 @@ conv3x3_c64_rows_kernel(int N, int H, const bf16* __restrict__ x, const bf16* __
       }
       const uint4 v = Chunk<bf16>::pack(f);
       *p = v;
-#if VLP_ACT_NT
-      typedef unsigned v4u_nt __attribute__((ext_vector_type(4)));
-      __builtin_nontemporal_store(v4u_nt{v.x, v.y, v.z, v.w},
-                                  reinterpret_cast<v4u_nt*>(xin.out + (((size_t)n * H + r) * kRcW + px) * 64 + cc * 8));
-#else
       stg16(xin.out + (((size_t)n * H + r) * kRcW + px) * 64 + cc * 8, v);
-#endif
     }
   };
 
@@ -1951,7 +1780,7 @@ static int launch_wgrad_rows(const ConvGeom& g, const void* dy, const void* x, f
 // c+1's pieces are issued over the first half-steps of chunk c, so the in-order
 // vmcnt wait for each B half-tile never waits on a whole window.  Workgroup
 // geometry: 8 waves, 4 (M) x 2 (N), 64 x BN/2 per wave (MFMA 16x16x32), in two
-// ping-pong groups (below); the epilogue is the multi-stage kernels'
+// ping-pong groups (below); the epilogue is the LDS-DMA GEMM kernels'
 // ms_epilogue<256, BN, 4, 2>.  (r5: a lock-step 8-wave form, a persistent forward
 // and timing-experiment builds were measured against this one and removed; their
 // records are profiles/r5q3_window_pingpong_ab.txt, r5p3_window_persistent_ab.txt,
@@ -2171,8 +2000,6 @@ static int launch_winpp_t(const ConvGeom& g, int cin, int nout, const void* x, c
   sh.kchunk = sh.K;
   sh.tiles_m = sh.M / 256;
   sh.tiles_n = nout / BN;
-  sh.xsplit = 0;
-  sh.dbg = 0;
   sh.nsplit = 1;
   KMat<bf16> lb{(const bf16*)w, sh.K, nout, sh.K};
   hipLaunchKernelGGL((conv3x3_winpp_kernel<TW, BN, FLIP, EP>), dim3(sh.tiles_m * sh.tiles_n), dim3(512), lds, st,
@@ -2435,9 +2262,6 @@ __global__ void __launch_bounds__(256) wgrad_fold_row_kernel(int C, int T, int k
   }
 }
 
-#ifndef VLP_WGRAD_SLOT_DIV
-#define VLP_WGRAD_SLOT_DIV 1   // weight-gradient split count sized for 1/DIV of the chip's slots
-#endif
 template <typename T>
 static int conv_wgrad_ws_t(const void* dy, const void* x, float* ws, long long ws_floats, int* ks_out, ConvGeom g,
                            hipStream_t st) {
@@ -2453,9 +2277,8 @@ static int conv_wgrad_ws_t(const void* dy, const void* x, float* ws, long long w
     // layer 1: the row-streaming kernel, one slab per workgroup
     if (wgrad_rows_ok(g)) return launch_wgrad_rows(g, dy, x, ws, max_ks, ks_out, st);
     // tile engines whose epilogue honours per-split output slabs
-    if (gemm_variant() >= 5 && g.K % 4 == 0) {
-      constexpr int mink5 = 2048;
-      int mink = g.Co <= 64 ? 2048 : mink5;
+    if (g.K % 4 == 0) {
+      int mink = 2048;
       const int need = (g.M + max_ks - 1) / max_ks;
       if (mink < need) mink = need;
       static_assert(use_bk<bf16, MNMat<bf16>, ConvWgradB<bf16, false>>(),
@@ -2463,10 +2286,8 @@ static int conv_wgrad_ws_t(const void* dy, const void* x, float* ws, long long w
       MNMat<bf16> la{(const bf16*)dy, g.Co, g.Co, g.M};
       ConvWgradB<bf16, false> lb{g, (const bf16*)x, nullptr, nullptr, g.K, make_pixstep(g, Elem<bf16>::BK)};
       EpiSplitStore ep{nullptr, nullptr, ws, g.K, slab};
-      ksplit_slot_div() = VLP_WGRAD_SLOT_DIV;
       const int r = g.Co <= 64 ? gemm_short<bf16>(g.Co, g.K, g.M, -mink, la, lb, ep, st)
                                : gemm_conv_wide<bf16>(g.Co, g.K, g.M, -mink, la, lb, ep, st);
-      ksplit_slot_div() = 1;
       if (r) return r;
       ks = last_ksplit();
       if (ks > max_ks) return (int)hipErrorInvalidValue;   // would have overrun the workspace
@@ -2757,7 +2578,7 @@ VLP_EXPORT int vlp_conv_dgrad_relu2(int dtype, const void* dy, const void* wt, v
                                     double* stat2, double* stat3, int stat_rep, void* stream) {
   ConvGeom g0 = make_geom(N, H, W, C, Co, KH, KW, S, P);
   // row-chunk epilogue kernels only: bf16 LDS-DMA engine, stride 1, N = C >= 128, K a multiple of 64
-  if (dtype != VLP_BF16 || gemm_variant() < 5 || S != 1 || C < 128 || C % 64 || Co % 64 || !relu_mask || !y ||
+  if (dtype != VLP_BF16 || S != 1 || C < 128 || C % 64 || Co % 64 || !relu_mask || !y ||
       !yd || !mean || !invstd || !meand || !invstdd || !stat1 || !stat2 || !stat3)
     return (int)hipErrorInvalidValue;
   ConvGeom g1 = g0;
@@ -2922,7 +2743,7 @@ VLP_EXPORT int vlp_stem_wgrad_ws(int dtype, const void* dy, const void* xp, floa
   const long long fit = ws_floats / slab;
   const int max_ks = (int)(fit < 4096 ? fit : 4096);
   if (max_ks < 1) return (int)hipErrorInvalidValue;
-  if (dtype != VLP_BF16 || gemm_variant() < 4) {   // other engines: atomics into slab 0
+  if (dtype != VLP_BF16) {   // fp32 parity mode: atomics into slab 0
     if (hipMemsetAsync(split_ws, 0, slab * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
     *nsplit = 1;
     return vlp_stem_wgrad(dtype, dy, xp, split_ws, N, H, W, stream);

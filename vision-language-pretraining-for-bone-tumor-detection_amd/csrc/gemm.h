@@ -25,19 +25,21 @@
 // 4 waves (256 threads) per workgroup in a WGM x WGN wave grid; the grid is
 // remapped so that consecutive tile ids share an XCD (L2 reuse of the A panel).
 // Split-K over grid.y for reductions over pixels (weight gradients).
+//
+// Kernels and the loader protocol each consumes (described where it is used):
+//   gemm_kernel (any dtype)       register staging: fixed / load; a bf16
+//                                 K-contig kDirect loader (KMat) is staged
+//                                 direct-to-LDS instead: start / step / next
+//   gemm_bk_kernel, gemm_big_kernel, gemm_pp_kernel (bf16)
+//                                 buffer protocol (kBuf): rsrc, bstart / bstep /
+//                                 boff (K-contig), brstart / bcstart / boff /
+//                                 bradvance (MN-contig)
 #pragma once
 #include <mutex>
 #include <type_traits>
 #include <utility>
 #include <vector>
 #include "common.h"
-
-#ifndef VLP_BIG_SCHED   // gemm_big_kernel instruction interleaving (0: compiler order)
-#define VLP_BIG_SCHED 0
-#endif
-#ifndef VLP_BIG_PRIO    // gemm_big_kernel: s_setprio 1 for waves 4-7
-#define VLP_BIG_PRIO 0
-#endif
 
 namespace vlp {
 
@@ -47,9 +49,7 @@ struct GemmShape {
   int M, N, K;
   int kchunk;   // K range per split (multiple of BK); == K rounded up when no split
   int tiles_m, tiles_n;
-  int xsplit;   // 1: split-K grid is 1-D and every split's tiles share one XCD
-  int dbg;      // reserved (0)
-  int nsplit;   // K-splits (bk / big kernels: 1-D grid of nsplit * tiles)
+  int nsplit;   // K-splits (LDS-DMA kernels: 1-D grid of nsplit * tiles; gemm_kernel splits over grid.y)
 };
 
 // ---------------- LDS image addressing (bytes) ----------------
@@ -64,7 +64,7 @@ __device__ __forceinline__ int mn_off(int k, int byte_in_row) {
   return k * RB + ((((byte_in_row >> 5) ^ sw) << 5) | (byte_in_row & 31));
 }
 
-// Blocked MN-contig image (direct staging): 1-KiB blocks of 8 k-rows x 8
+// Blocked MN-contig image (LDS-DMA staging): 1-KiB blocks of 8 k-rows x 8
 // 16-B chunks, block (k>>3, c>>3) at ((k>>3)*CPB + (c>>3)) KiB (CPB = chunk
 // blocks per k-row = MN/64); inside a block, chunk c&7 of row k&7 sits at
 // 16*((c&7) ^ h(k)), h = bit1(k)<<1 | bit3(k)<<2: the two 32-lane halves of a
@@ -106,6 +106,11 @@ struct TileGeom {
   static_assert(KC || (256 % CPR == 0), "MN tile geometry");
 };
 
+// Register-staging loader protocol (every loader; consumed by gemm_kernel):
+//   State fixed(int coord)              once per chunk row (K-contig) or chunk
+//                                       column (MN-contig) of the thread
+//   uint4 load(const State&, int k)     one 16-B chunk at reduction index k,
+//                                       zeros outside the operand
 // Per-thread staging of one operand tile into registers and then LDS.
 template <typename T, int BM, class L>
 struct Stager {
@@ -149,18 +154,21 @@ struct Stager {
 };
 
 // ---------------- direct-to-LDS staging (bf16) ----------------
-// Loaders that can name the global address of a chunk (kDirect = true) are
-// staged with global_load_lds_dwordx4: each wave-instruction writes 1 KiB of
+// A K-contig loader that can name the global address of a chunk (kDirect =
+// true; KMat only) is staged by gemm_kernel with global_load_lds_dwordx4 when
+// it meets a partner that keeps the pair off the buffer-protocol kernels (a
+// transforming convolution loader): each wave-instruction writes 1 KiB of
 // LDS lane-linearly, so lane L of instruction i fills PHYSICAL chunk
 // q = (wave*NI + i)*64 + L and fetches the LOGICAL chunk that the XOR swizzle
 // places there (the swizzles are involutions).  No staging registers, no
 // ds_write pass; the loads of tile t+1 fly while tile t is multiplied.
 //
-// Direct loaders are INCREMENTAL (profiling showed ~8 VALU per MFMA when every
-// chunk address was rebuilt from scratch each K-step):
-//   DState start(int coord, int koff, int kb)  once per chunk: coord = the
-//        operand row (K-contig) or first row of the chunk (MN-contig), koff = the
-//        chunk's k offset inside a K-step, kb = the first K-step's base
+// Direct loader protocol (consumed by gemm_kernel's GStager), INCREMENTAL
+// (profiling showed ~8 VALU per MFMA when every chunk address was rebuilt from
+// scratch each K-step):
+//   DState start(int row, int koff, int kb)    once per chunk: row = the
+//        operand row, koff = the chunk's k offset inside a K-step, kb = the
+//        first K-step's base
 //   Step step(int k0)                           once per K-step per wave: the
 //        k0-only context (conv tap, channel offset, K bound) -- wave-uniform,
 //        so it lives in scalar registers and is shared by all NI chunks
@@ -273,10 +281,9 @@ struct GStager {
   }
 };
 
-// Uniform staging interface: register staging (any loader, fp32 parity mode,
-// transforming loaders) or direct-to-LDS (bf16 + kDirect loaders).
-// (the 2-stage kernel stages MN-contig operands through registers; direct
-// MN staging lives in the multi-stage kernel)
+// Uniform staging interface of gemm_kernel: register staging (any loader, fp32
+// parity mode, transforming loaders, every MN-contig operand) or direct-to-LDS
+// (bf16 + K-contig kDirect loaders).
 template <typename T, int BM, class L,
           bool DIRECT = (sizeof(T) == 2) && DirectTrait<L>::value && L::kKContig>
 struct OpStager;
@@ -301,8 +308,8 @@ struct OpStager<T, BM, L, true> {
 // k-permutation shared by both operands, chosen so a K-contig fragment is ONE
 // 16-B chunk (ds_read_b128, conflict-free under the kc_off swizzle) and an
 // MN-contig fragment is two ds_read_b64_tr_b16 (k-rows 32s+8g+q, +4).
-// MNCOL: MN-contig image in the blocked layout of the direct MN stager
-// (GStagerN<..., false>, mn8_off): 1-KiB blocks of 8 k-rows x 8 chunks.
+// MNCOL: MN-contig image in the blocked layout of the LDS-DMA MN stager
+// (BStager<..., false>, mn8_off): 1-KiB blocks of 8 k-rows x 8 chunks.
 template <bool KC, int RB, bool MNCOL = false>
 __device__ __forceinline__ v8bf frag_bf16(const char* lds, int rb, int s) {
   const int l = threadIdx.x & 63;
@@ -560,88 +567,10 @@ gemm_kernel(GemmShape sh, LA la, LB lb, EP ep) {
   }
 }
 
-// ---------------- multi-stage direct-to-LDS kernel (bf16) ----------------
-// S-slot LDS ring: tiles t+1 .. t+S-2 stay in flight while tile t is
-// multiplied.  Per K-step: wait (counted vmcnt: this wave's loads of tile t
-// have landed), raw s_barrier (every wave's have; every wave finished tile
-// t-1, whose slot is refilled next), issue tile t+S-1, compute tile t.  A
-// __syncthreads() would drain the ring (an LDS-DMA is a pending VM op), so
-// the wait and barrier are explicit.
-template <typename T, int BM, class L, int NT, bool KC = L::kKContig>
-struct GStagerN;
-// K-contig operand: [BM rows][128 B] image, 16-B chunks XOR-swizzled by row.
-template <typename T, int BM, class L, int NT>
-struct GStagerN<T, BM, L, NT, true> {
-  static constexpr int NI = BM * 8 / NT;   // 16-B chunks (= 1 KiB wave-instructions) per thread
-  static_assert(NI >= 1 && (BM * 8) % NT == 0, "tile / thread geometry");
-  typename L::DState st[NI];
-  __device__ __forceinline__ void init(const L& ld, int row0, int kb) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int q = (w * NI + i) * 64 + lane;
-      const int r = q >> 3, p = q & 7;
-      st[i] = ld.start(row0 + r, (p ^ ((r >> 1) & 7)) * Elem<T>::EPC, kb);
-    }
-  }
-  __device__ __forceinline__ void issue(const L& ld, int k0, char* lds, bool = false) {
-    const int w = threadIdx.x >> 6;
-    const auto stp = ld.step(k0);   // K-step-uniform context (scalar registers)
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const void* p = ld.next(st[i], stp);
-      __builtin_amdgcn_global_load_lds(p, (__attribute__((address_space(3))) void*)(lds + (w * NI + i) * 1024),
-                                       16, 0, 0);
-    }
-  }
-};
-// MN-contig operand, blocked image (mn8_off): wave w's instruction i fills
-// 1-KiB block b = w*NI + i = (k-row block b / CPB, chunk block b % CPB), lane
-// L row k = 8*(b / CPB) + L/8 -- 8 full 128-B lines per instruction.  The
-// loader's per-k state (e.g. the output pixel of a weight-gradient
-// reduction) is walked once per distinct row of the thread (NI / CPB rows)
-// and combined with a fixed offset per chunk column:
-//   RState rstart(int k, int kb); void radvance(RState&)      per k-row
-//   CState cstart(int mn)                                      per column
-//   const void* addr(const RState&, const CState&)             address / zero page
-template <typename T, int BM, class L, int NT>
-struct GStagerN<T, BM, L, NT, false> {
-  static constexpr int NW = NT / 64;
-  static constexpr int CPB = BM / 64;              // chunk blocks per k-row block
-  static constexpr int NI = 8 * CPB / NW;          // 1-KiB blocks per thread
-  static constexpr int NR = NI >= CPB ? NI / CPB : 1;   // distinct k-rows per thread
-  static_assert(NI >= 1 && (8 * CPB) % NW == 0 && (NI % CPB == 0 || CPB % NI == 0), "tile / thread geometry");
-  static_assert(sizeof(T) == 2, "MN direct staging is bf16 (BK = 64 rows)");
-  typename L::RState rs[NR];
-  typename L::CState cs[NI];
-  __device__ __forceinline__ void init(const L& ld, int row0, int kb) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int b = w * NI + i;
-      const int k = 8 * (b / CPB) + (lane >> 3);
-      const int c = 8 * (b % CPB) + ((lane & 7) ^ mn8_h(k));
-      cs[i] = ld.cstart(row0 + c * 8);
-      if (i % CPB == 0 || NI < CPB) {
-        if (i / CPB < NR) rs[i / CPB] = ld.rstart(k, kb);
-      }
-    }
-  }
-  __device__ __forceinline__ void issue(const L& ld, int, char* lds, bool freeze = false) {
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const void* p = ld.addr(rs[NI >= CPB ? i / CPB : 0], cs[i]);
-      __builtin_amdgcn_global_load_lds(p, (__attribute__((address_space(3))) void*)(lds + (w * NI + i) * 1024),
-                                       16, 0, 0);
-    }
-    if (!freeze) {
-#pragma unroll
-      for (int r = 0; r < NR; ++r) ld.radvance(rs[r]);
-    }
-  }
-};
-
+// ---------------- LDS-DMA kernels (bf16): shared pieces ----------------
+// An LDS-DMA is a pending VM op, so a __syncthreads() would drain the ring of
+// tiles in flight: the kernels below wait on a counted vmcnt (this wave's loads
+// of the tile have landed) and a raw s_barrier (every wave's have).
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -654,13 +583,7 @@ __device__ __forceinline__ double* stat3_of(const EP& ep) {
   else return nullptr;
 }
 
-// timing experiments only (wrong results): 1 = staged epilogues skip their
-// global stores, 2 = staged epilogues skip the statistics reduction + atomics,
-// 3 = row epilogues skip their operand loads (pre8)
-#ifndef VLP_EPI_EXP
-#define VLP_EPI_EXP 0
-#endif
-// Epilogue shared by the multi-stage kernels: lane l = 16g + i owns
+// Epilogue shared by the LDS-DMA kernels: lane l = 16g + i owns
 // C[row = rbase + i][col = cbase + 4g .. 4g+3] of each 16x16 block.
 // LP: the row epilogue's operand slot kLdsSlot comes from the LDS image lds_pre.
 // RAW (staged epilogues): the workgroup syncs are LDS-only (lgkmcnt + s_barrier,
@@ -739,7 +662,7 @@ __device__ __forceinline__ void ms_epilogue(const GemmShape& sh, const EP& ep, v
 #pragma unroll
     for (int i = 0; i < D; ++i) {
       const int r = r0 + i * RS;
-      if (VLP_EPI_EXP != 3 && cok && r < BM && row0 + r < sh.M) pre_load(row0 + r, pre[i]);
+      if (cok && r < BM && row0 + r < sh.M) pre_load(row0 + r, pre[i]);
     }
     float cf[NCF > 0 ? NCF : 1][8];
     if constexpr (NCF > 0) {
@@ -767,7 +690,7 @@ __device__ __forceinline__ void ms_epilogue(const GemmShape& sh, const EP& ep, v
       if constexpr (LS >= 0) cur.u[LS] = *reinterpret_cast<const uint4*>(lds_pre + r * (BN * 2) + c * 16);
       if (i + D < NIT) {
         const int rn = r + D * RS;
-        if (VLP_EPI_EXP != 3 && cok && rn < BM && row0 + rn < sh.M) pre_load(row0 + rn, pre[i % D]);
+        if (cok && rn < BM && row0 + rn < sh.M) pre_load(row0 + rn, pre[i % D]);
       }
       if (cok && r < BM && row < sh.M) {
         float v[8];
@@ -850,11 +773,11 @@ __device__ __forceinline__ void ms_epilogue(const GemmShape& sh, const EP& ep, v
     for (int q = threadIdx.x; q < BM * CPR; q += NT) {
       const int r = q / CPR, c = q - r * CPR;
       const int row = row0 + r, col = col0 + c * 8;
-      if (VLP_EPI_EXP != 1 && row < sh.M && col < sh.N)
+      if (row < sh.M && col < sh.N)
         ep.store8(row, col, *reinterpret_cast<const uint4*>(stg + r * BN + ((c ^ (r & (CPR - 1))) << 3)));
     }
   }
-  if constexpr (EP::kStats && VLP_EPI_EXP != 2) {
+  if constexpr (EP::kStats) {
     epi_sync();
     const int rep = ep.stat_rep > 1 ? (wid % ep.stat_rep) : 0;
     for (int cl = threadIdx.x; cl < BN; cl += NT) {
@@ -870,120 +793,16 @@ __device__ __forceinline__ void ms_epilogue(const GemmShape& sh, const EP& ep, v
   }
 }
 
-template <int BM, int BN, int WGM, int WGN, int S, class LA, class LB, class EP>
-__global__ void __launch_bounds__(WGM * WGN * 64)
-gemm_ms_kernel(GemmShape sh, LA la, LB lb, EP ep) {
-  using T = bf16;
-  constexpr int NT = WGM * WGN * 64;
-  constexpr int WTM = BM / WGM, WTN = BN / WGN;
-  constexpr int MB = WTM / 16, NB = WTN / 16;
-  constexpr int BK = 64;
-  using GA = TileGeom<T, BM, LA::kKContig>;
-  using GB = TileGeom<T, BN, LB::kKContig>;
-  constexpr int ABYTES = BM * 128;
-  constexpr int STAGE = (BM + BN) * 128;
-  using SA = GStagerN<T, BM, LA, NT>;
-  using SB = GStagerN<T, BN, LB, NT>;
-  constexpr int NI = SA::NI + SB::NI;   // VM ops per thread per tile
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  const int nwg = sh.tiles_m * sh.tiles_n;
-  const int bid = blockIdx.x;
-  int wid = bid, split = blockIdx.y;
-  if (sh.xsplit) {
-    // split-K reductions re-read their K slice once per tile: keep all tiles of
-    // a split on one XCD (dispatch is round-robin over XCDs) so the slice is
-    // fetched into ONE L2 instead of eight
-    const int xcd = bid & 7, j = bid >> 3, jt = j / nwg;
-    split = xcd + 8 * jt;
-    wid = j - jt * nwg;
-  } else if (nwg >= 16) {
-    const int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, rr = nwg & 7;
-    wid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
-  const int tm = wid / sh.tiles_n, tn = wid - tm * sh.tiles_n;
-  const int row0 = tm * BM, col0 = tn * BN;
-  const int kb = split * sh.kchunk;
-  int ke = kb + sh.kchunk;
-  if (ke > sh.K) ke = sh.K;
-  const int nk = (ke - kb + BK - 1) / BK;
-  const int wave = threadIdx.x >> 6;
-  const int wm = wave / WGN, wn = wave - wm * WGN;
-
-  SA sa;
-  SB sb;
-  sa.init(la, row0, kb);
-  sb.init(lb, col0, kb);
-  v4f acc[MB][NB];
-#pragma unroll
-  for (int a = 0; a < MB; ++a)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[a][b] = v4f{0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int s = 0; s < S - 1; ++s) {
-    if (s < nk) {
-      sa.issue(la, kb + s * BK, smem + s * STAGE);
-      sb.issue(lb, kb + s * BK, smem + s * STAGE + ABYTES);
-    }
-  }
-  int slot = 0;                 // slot of tile t
-  int fill = S - 1;             // slot receiving tile t + S - 1
-  for (int t = 0; t < nk; ++t) {
-    // tiles issued after t so far: min(t + S - 2, nk - 1) - t
-    const int ahead = (t + S - 2 < nk - 1 ? S - 2 : nk - 1 - t);
-    if constexpr (S >= 4) {
-      if (ahead >= 2) wait_vmcnt<2 * NI>();
-      else if (ahead == 1) wait_vmcnt<NI>();
-      else wait_vmcnt<0>();
-    } else if constexpr (S == 3) {
-      if (ahead >= 1) wait_vmcnt<NI>();
-      else wait_vmcnt<0>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    raw_barrier();
-    // All fragments of tile t are read BEFORE tile t+S-1 is issued: hipcc
-    // cannot tell a ds_read_b64_tr_b16 from a read of the DMA target and
-    // would otherwise drain the just-issued loads (s_waitcnt vmcnt(0)) in
-    // front of the first transposed read, serialising load and compute.
-    const char* ia = smem + slot * STAGE;
-    const char* ib = ia + ABYTES;
-    v8bf fa[2][MB], fb[2][NB];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int a = 0; a < MB; ++a) fa[s][a] = frag_bf16<LA::kKContig, GA::RB, true>(ia, wm * WTM + a * 16, s);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) fb[s][b] = frag_bf16<LB::kKContig, GB::RB, true>(ib, wn * WTN + b * 16, s);
-    }
-    if (t + S - 1 < nk) {
-      char* f = smem + fill * STAGE;
-      sa.issue(la, kb + (t + S - 1) * BK, f, false);
-      sb.issue(lb, kb + (t + S - 1) * BK, f + ABYTES, false);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-#pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[s][b], fa[s][a], acc[a][b], 0, 0, 0);
-    }
-    slot = (slot + 1 == S) ? 0 : slot + 1;
-    fill = (fill + 1 == S) ? 0 : fill + 1;
-  }
-  __syncthreads();   // all waves done with the ring before the epilogue reuses LDS
-
-  static_assert(!StageTrait<EP>::value || 4096 + BM * BN * 2 <= S * STAGE, "staging tile fits the ring");
-  ms_epilogue<BM, BN, WGM, WGN, EP>(sh, ep, acc, row0, col0, wid, wm, wn, smem);
-}
-
 // ---------------- buffer-DMA two-slot kernel (bf16) ----------------
-// The same engine as gemm_ms_kernel with S = 2, restated for a lower VALU
-// cost per K-step (profiling: 4-8 VALU per MFMA in the direct kernels, more
-// than the two-waves-per-SIMD issue budget of ~2):
+// Two-slot LDS ring: tile t+1 is in flight while tile t is multiplied.  Per
+// K-step: vmcnt(0) + raw barrier (every wave's loads of tile t have landed and
+// every wave finished tile t-1, whose slot is refilled next), read all
+// fragments of tile t, issue tile t+1, compute tile t.  All fragments are read
+// BEFORE the next tile is issued: hipcc cannot tell a ds_read_b64_tr_b16 from
+// a read of the DMA target and would otherwise drain the just-issued loads in
+// front of the first transposed read, serialising load and compute.
+// Built for a low VALU cost per K-step (the two-waves-per-SIMD issue budget is
+// ~2 VALU per MFMA):
 //  * operands are fetched with buffer_load ... lds through a buffer resource
 //    (base + 32-bit byte offset): an out-of-range chunk is an offset past
 //    num_records (kOOB), which the hardware returns as zeros, so no zero-page
@@ -993,12 +812,18 @@ gemm_ms_kernel(GemmShape sh, LA la, LB lb, EP ep) {
 //    wave-uniform base held in SGPRs;
 //  * a K-step past the end issues through a null resource (num_records = 0)
 //    instead of branching, so the loop body stays one basic block.
-// Loader protocol (kBuf = true):
+// Buffer loader protocol (kBuf = true; consumed by gemm_bk_kernel,
+// gemm_big_kernel and gemm_pp_kernel through BStager / HStager):
 //   rsrc_t rsrc() const                                     whole-operand resource
-//   K-contig: BState bstart(int row, int koff, int kb); BStep bstep(int k0);
+//   K-contig: BState bstart(int row, int koff, int kb)      once per chunk
+//             BStep bstep(int k0)                           once per K-step (wave-uniform)
 //             unsigned boff(BState&, const BStep&)          byte offset | kOOB
-//   MN-contig: BRow brstart(int k, int kb); BCol bcstart(int mn);
-//             unsigned boff(const BRow&, const BCol&); void bradvance(BRow&)
+//   MN-contig (blocked image, mn8_off: the loader's per-k state, e.g. the output
+//   pixel of a weight-gradient reduction, is walked once per distinct k-row of
+//   the thread and combined with a fixed offset per chunk column):
+//             BRow brstart(int k, int kb); void bradvance(BRow&)   per k-row
+//             BCol bcstart(int mn)                                 per column
+//             unsigned boff(const BRow&, const BCol&)              byte offset | kOOB
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 constexpr unsigned kOOB = 0x80000000u;   // every operand is < 2 GiB (checked on the host)
 
@@ -1056,7 +881,9 @@ struct BStager<BM, L, NT, true> {
     for (int i = 0; i < NI; ++i) dma16(rs, ld.boff(st[i], stp), lds + (wv * NI + i) * 1024);
   }
 };
-// MN-contig operand, blocked image (mn8_off), as GStagerN.
+// MN-contig operand, blocked image (mn8_off): wave w's instruction i fills
+// 1-KiB block b = w*NI + i = (k-row block b / CPB, chunk block b % CPB), lane
+// L row k = 8*(b / CPB) + L/8 -- 8 full 128-B lines per instruction.
 template <int BM, class L, int NT>
 struct BStager<BM, L, NT, false> {
   static constexpr int NW = NT / 64;
@@ -1289,11 +1116,6 @@ gemm_big_kernel(GemmShape sh, LA la, LB lb, EP ep) {
     else return frag_tr_sub<BN * 2, b>(bbase[decltype(slc)::value][b & 3], s);
   };
 
-#if VLP_BIG_PRIO
-  // static priority for the second-dispatched half (MI355X_MICROARCH.md, "Two waves
-  // per SIMD" item 4): waves 4-7 are the arbitration losers on every segment
-  if (wv >= (WGM * WGN) / 2) __builtin_amdgcn_s_setprio(1);
-#endif
   auto body = [&](auto slc, int t) __attribute__((always_inline)) {
     constexpr int SL = decltype(slc)::value;
     wait_vmcnt<NI>();
@@ -1312,17 +1134,6 @@ gemm_big_kernel(GemmShape sh, LA la, LB lb, EP ep) {
 #pragma unroll
       for (int b = 0; b < NB; ++b)
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[0][b], fa[0][a], acc[a][b], 0, 0, 0);
-#if VLP_BIG_SCHED >= 2
-    // K-contig operands: the substep-1 fragment reads trail the substep-0 MFMAs
-    // (one ds_read_b128 per two MFMAs) instead of bursting before them
-    if constexpr (LA::kKContig && LB::kKContig) {
-#pragma unroll
-      for (int q = 0; q < MB + NB; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x0100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x0008, 2, 0);
-      }
-    }
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     raw_barrier();
     const bool live = t + 2 < nk;
@@ -1335,18 +1146,6 @@ gemm_big_kernel(GemmShape sh, LA la, LB lb, EP ep) {
 #pragma unroll
       for (int b = 0; b < NB; ++b)
         acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[1][b], fa[1][a], acc[a][b], 0, 0, 0);
-#if VLP_BIG_SCHED >= 1
-    // the next tile's LDS-DMA pieces spread over the substep-1 MFMAs (one per
-    // MB*NB/NI MFMAs) instead of a burst in which the SIMD's matrix pipe idles
-    {
-      constexpr int PER = (MB * NB) / NI > 0 ? (MB * NB) / NI : 1;
-#pragma unroll
-      for (int q = 0; q < NI; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x0010, 1, 1);
-        __builtin_amdgcn_sched_group_barrier(0x0008, PER, 1);
-      }
-    }
-#endif
   };
   int t = 0;
   if (nk & 1) {
@@ -1395,11 +1194,6 @@ constexpr int big_lds_bytes() {
 // issue in the MFMA gaps, MI355X guide 8-phase template)
 #ifndef VLP_PP_PRIO
 #define VLP_PP_PRIO 1
-#endif
-// timing experiments only (wrong results): 1 = no LDS-DMA issue, 2 = no fragment
-// reads, 3 = no MFMAs (tools/build_variant.sh; never in the product library)
-#ifndef VLP_PP_EXP
-#define VLP_PP_EXP 0
 #endif
 __device__ __forceinline__ int pp_chunk(int r, int c) { return c ^ (((r >> 3) & 1) << 1); }
 template <int BM, class L, int NTG, bool KC = L::kKContig>
@@ -1543,10 +1337,7 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
     if constexpr (G == 0) ss.init(la, row0, kb, wg);
     else ss.init(lb, col0, kb, wg);
     auto fetch = [&](auto hc, int u, char* slot) __attribute__((always_inline)) {
-      if constexpr (VLP_PP_EXP == 1) return;
-      if constexpr (VLP_PP_EXP == 6 && G == 0) if (((u >> 1) % 9) != 0) return;   // A bytes / 9
-      if constexpr (VLP_PP_EXP == 7 && G == 1) if (((u >> 1) % 9) != 0) return;   // B bytes / 9
-      const int k0 = VLP_PP_EXP == 5 ? kb + (u >> 1) * BK : kperm_of(la, kb + (u >> 1) * BK);
+      const int k0 = kperm_of(la, kb + (u >> 1) * BK);
       if constexpr (G == 0) ss.template issue<decltype(hc)::value>(la, u < nh ? ra : rz, k0, slot, wg);
       else ss.template issue<decltype(hc)::value>(lb, u < nh ? rb : rz, k0, slot + HA, wg);
     };
@@ -1570,12 +1361,6 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
       constexpr int SL = decltype(slc)::value;
       constexpr int SO = (SL & 1) * SLOT;   // offset inside the slot pair
       v8bf fa[MB], fb[NB];
-      if constexpr (VLP_PP_EXP == 2) {
-#pragma unroll
-        for (int a = 0; a < MB; ++a) fa[a] = v8bf{};
-#pragma unroll
-        for (int b = 0; b < NB; ++b) fb[b] = v8bf{};
-      } else {
       static_for<0, MB>([&](auto ac) {
         constexpr int a = decltype(ac)::value;
         if constexpr (LA::kKContig)
@@ -1590,7 +1375,6 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
         else
           fb[b] = frag_tr_at<SO + (b >> 2) * 1024>(bbase[SL >> 1][b & 3]);
       });
-      }
       v4f xs0, xs1, xh0, xh1;
       unsigned xtap = 0;
       if constexpr (XA) {
@@ -1619,26 +1403,11 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
 #pragma unroll
         for (int a = 0; a < MB; ++a) fa[a] = bn_relu_frag(fa[a], xs0, xs1, xh0, xh1, (xm[a / 3] >> (xtap + 9 * (a % 3))) & 1u);
       }
-      if constexpr (VLP_PP_EXP == 4 && NB == 4) {   // 32x32x16 issue pattern (wrong layout)
-        typedef float v16f_ __attribute__((ext_vector_type(16)));
-#pragma unroll
-        for (int a = 0; a < MB; ++a) {
-          v16f_ t = *reinterpret_cast<v16f_*>(&acc[a][0]);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[a & 3], fa[a], t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[(a + 1) & 3], fa[a], t, 0, 0, 0);
-          *reinterpret_cast<v16f_*>(&acc[a][0]) = t;
-        }
-      } else if constexpr (VLP_PP_EXP != 3) {
 #pragma unroll
       for (int a = 0; a < MB; ++a)
 #pragma unroll
         for (int b = 0; b < NB; ++b)
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[b], fa[a], acc[a][b], 0, 0, 0);
-      } else {
-#pragma unroll
-      for (int a = 0; a < MB; ++a)
-        acc[a][0][0] += (float)fa[a][0] + (float)fb[0][0];
-      }
 #if VLP_PP_PRIO
       __builtin_amdgcn_s_setprio(0);
 #endif
@@ -1671,26 +1440,20 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
   }
 }
 
-// Split-K count for a reduction of K over `tiles` output tiles, given the
-// number of workgroups the chip holds at once (`slots`).  Workgroups of one
-// launch all cost about the same, so the launch takes ceil(WG / slots)
-// rounds: pick the split (1..4 rounds' worth) with the best slot fill, each
-// split still >= min_k deep (epilogue atomics amortised).
-// split count of the last launch_gemm_bk / launch_gemm_big call on this host
-// thread (callers of split-store epilogues size their fold pass with it)
+// split count of the last launch_gemm_bk / launch_gemm_big / launch_gemm_pp
+// call on this host thread (callers of split-store epilogues size their fold
+// pass with it)
 inline int& last_ksplit() {
   static thread_local int v = 1;
   return v;
 }
-// fraction of the chip's workgroup slots an auto-split launch is sized for
-// (1: all; the weight gradients on their side stream may take fewer, see
-// conv_wgrad_ws_t)
-inline int& ksplit_slot_div() {
-  static thread_local int v = 1;
-  return v;
-}
+// Split-K count for a reduction of K over `tiles` output tiles, given the
+// number of workgroups the chip holds at once (`slots`).  Workgroups of one
+// launch all cost about the same, so the launch takes ceil(WG / slots)
+// rounds: pick the split (1..4 rounds' worth) with the best slot fill, each
+// split still >= min_k deep (epilogue atomics amortised).  slots >= 1: the
+// launchers pass occupancy * CUs, both clamped to at least 1.
 inline int balanced_ksplit(int tiles, int K, int slots, int min_k) {
-  slots = slots / ksplit_slot_div() > 0 ? slots / ksplit_slot_div() : 1;
   if (tiles >= slots) return 1;
   int best = 1;
   double best_eff = 0.0;
@@ -1751,46 +1514,6 @@ inline int prepare_kernel(KernelDevState& s, const void* fn, int lds, int thread
   return 0;
 }
 
-template <int BM, int BN, int WGM, int WGN, int S, class LA, class LB, class EP>
-inline int launch_gemm_ms(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
-                          hipStream_t stream) {
-  constexpr int BK = 64;
-  if (M <= 0 || N <= 0) return 0;
-  GemmShape sh;
-  sh.xsplit = 0;
-  sh.nsplit = 1;
-  sh.dbg = 0;
-  sh.M = M; sh.N = N; sh.K = K;
-  sh.tiles_m = (M + BM - 1) / BM;
-  sh.tiles_n = (N + BN - 1) / BN;
-  constexpr int lds = S * (BM + BN) * 128;
-  static_assert(lds <= 160 * 1024, "LDS budget");
-  static KernelDevState kst;
-  if (ksplit <= 0) {   // auto: fill whole rounds of resident workgroups
-    int occ = 1;
-    const int e = prepare_kernel(kst, (const void*)&gemm_ms_kernel<BM, BN, WGM, WGN, S, LA, LB, EP>, lds, WGM * WGN * 64, &occ);
-    if (e) return e;
-    ksplit = balanced_ksplit(sh.tiles_m * sh.tiles_n, K, occ * device_cus(), -ksplit > 0 ? -ksplit : 2048);
-  }
-  if (ksplit < 1) ksplit = 1;
-  int kc = (K + ksplit - 1) / ksplit;
-  kc = ((kc + BK - 1) / BK) * BK;
-  if (kc < BK) kc = BK;
-  ksplit = (K + kc - 1) / kc;
-  if (ksplit < 1) ksplit = 1;
-  sh.kchunk = kc;
-  sh.xsplit = (ksplit >= 8 && ksplit % 8 == 0) ? 1 : 0;
-  dim3 grid = sh.xsplit ? dim3(sh.tiles_m * sh.tiles_n * ksplit, 1, 1)
-                        : dim3(sh.tiles_m * sh.tiles_n, ksplit, 1);
-  {
-    const int e = prepare_kernel(kst, (const void*)&gemm_ms_kernel<BM, BN, WGM, WGN, S, LA, LB, EP>, lds, 0, nullptr);
-    if (e) return e;
-  }
-  hipLaunchKernelGGL((gemm_ms_kernel<BM, BN, WGM, WGN, S, LA, LB, EP>), grid, dim3(WGM * WGN * 64), lds,
-                     stream, sh, la, lb, ep);
-  return (int)hipGetLastError();
-}
-
 template <int BM, int BN, int WGM, int WGN, class LA, class LB, class EP>
 inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
                           hipStream_t stream) {
@@ -1798,9 +1521,7 @@ inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const L
   constexpr int S = 2;
   if (M <= 0 || N <= 0) return 0;
   GemmShape sh;
-  sh.xsplit = 0;
   sh.nsplit = 1;
-  sh.dbg = 0;
   sh.M = M; sh.N = N; sh.K = K;
   sh.tiles_m = (M + BM - 1) / BM;
   sh.tiles_n = (N + BN - 1) / BN;
@@ -1820,7 +1541,6 @@ inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const L
   ksplit = (K + kc - 1) / kc;
   if (ksplit < 1) ksplit = 1;
   sh.kchunk = kc;
-  sh.xsplit = 0;
   sh.nsplit = ksplit;
   last_ksplit() = ksplit;
   dim3 grid(sh.tiles_m * sh.tiles_n * ksplit, 1, 1);
@@ -1840,9 +1560,7 @@ inline int launch_gemm_big(int M, int N, int K, int ksplit, const LA& la, const 
   constexpr int S = 2;
   if (M <= 0 || N <= 0) return 0;
   GemmShape sh;
-  sh.xsplit = 0;
   sh.nsplit = 1;
-  sh.dbg = 0;
   sh.M = M; sh.N = N; sh.K = K;
   sh.tiles_m = (M + BM - 1) / BM;
   sh.tiles_n = (N + BN - 1) / BN;
@@ -1862,7 +1580,6 @@ inline int launch_gemm_big(int M, int N, int K, int ksplit, const LA& la, const 
   ksplit = (K + kc - 1) / kc;
   if (ksplit < 1) ksplit = 1;
   sh.kchunk = kc;
-  sh.xsplit = 0;
   sh.nsplit = ksplit;
   last_ksplit() = ksplit;
   dim3 grid(sh.tiles_m * sh.tiles_n * ksplit, 1, 1);
@@ -1881,8 +1598,6 @@ inline int launch_gemm_pp(int M, int N, int K, int ksplit, const LA& la, const L
   constexpr int BK = 64;
   if (M <= 0 || N <= 0) return 0;
   GemmShape sh;
-  sh.xsplit = 0;
-  sh.dbg = 0;
   sh.M = M; sh.N = N; sh.K = K;
   sh.tiles_m = (M + BM - 1) / BM;
   sh.tiles_n = (N + BN - 1) / BN;
@@ -1917,145 +1632,23 @@ inline int launch_gemm_pp(int M, int N, int K, int ksplit, const LA& la, const L
 template <typename T, int BM, int BN>
 constexpr int gemm_lds_bytes() { return 2 * (BM + BN) * 128; }
 
-// ---------------- variant dispatch ----------------
-// bf16 + direct loaders -> multi-stage kernels; everything else -> the
-// register-staged 2-stage kernel.  VLP_GEMM_DEFAULT_VARIANT (compile time) selects among tile /
-// stage configurations (tools/build_variant.sh builds A/B libraries; the default is the measured best).
-#ifndef VLP_GEMM_DEFAULT_VARIANT
-#define VLP_GEMM_DEFAULT_VARIANT 5
-#endif
-inline int gemm_variant() {
-  return VLP_GEMM_DEFAULT_VARIANT;
-}
-template <typename T, class LA, class LB>
-constexpr bool use_ms() {
-  return std::is_same<T, bf16>::value && DirectTrait<LA>::value && DirectTrait<LB>::value;
-}
-template <typename T, class LA, class LB>
-constexpr bool use_bk() {
-  return std::is_same<T, bf16>::value && BufTrait<LA>::value && BufTrait<LB>::value;
-}
-// large-tile shape choice: 256x256 (8 waves, one workgroup per CU) when both
-// dimensions allow it, else 128x256, and 128x128 (4 waves) for N = 128
-template <class LA, class LB, class EP>
-inline int gemm_big_auto(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
-  // (256x256 keeps 128x64 fragments per wave live: only the all-K-contig case
-  // fits the 256-VGPR budget without spilling)
-  // ping-pong schedule (gemm_pp_kernel): 1 = K-contig x K-contig, 2 = also MN x MN
-  // (default 2, measured per step: K-contig +0.4-0.8 % (the 256x256 forward /
-  // data-gradient GEMMs +3 %), MN x MN weight gradients another +2.4 % (layers
-  // 3-4 +10-19 %); the 128x256 MN tiles of layer 2 lose (-10 %) and stay on
-  // gemm_big_kernel, as do 256x128 K-contig tiles)
-  constexpr int pp = 2;   // ping-pong kernel for K-contig 256x256 and MNxMN weight gradients
-  constexpr bool kk = LA::kKContig && LB::kKContig;
-  constexpr bool mm = !LA::kKContig && !LB::kKContig;
-  if constexpr (kk || mm) {
-    if (pp >= (kk ? 1 : 2) && M >= 256 && N >= 256 && K % 64 == 0)
-      return launch_gemm_pp<256, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if constexpr (mm) {
-    // Co = 128 weight gradients (layer 2, N = 9 * 128 = 3 * 384): 128x384 tiles,
-    // a 64x96 per-wave tile (20 transposing reads per 24 MFMAs)
-    if (pp >= 2 && pp != 7 && M > 64 && M <= 128 && N % 384 == 0 && K % 64 == 0)
-      return launch_gemm_pp<128, 384, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if constexpr (kk) {
-    if (M >= 256 && N >= 256) return launch_gemm_big<256, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if (N >= 256) return launch_gemm_big<128, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
-  // N = 128: 128x128 tiles (4 waves, 64 KB ring) run two workgroups per CU, so
-  // one tile's epilogue overlaps the other's main loop (layer 2, K = 1152 is
-  // only 18 K-steps per tile); measured +1 % per step over 256x128
-  constexpr int n128 = 1;
-  if (n128 == 1) return launch_gemm_big<128, 128, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
-  return launch_gemm_big<256, 128, 4, 2>(M, N, K, ksplit, la, lb, ep, st);
-}
-// N >= 128 columns
-template <typename T, class LA, class LB, class EP>
-inline int gemm_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
-                     hipStream_t st) {
-  if constexpr (use_bk<T, LA, LB>()) {
-    if (gemm_variant() >= 4) return launch_gemm_bk<128, 128, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if constexpr (use_ms<T, LA, LB>()) {
-    switch (gemm_variant()) {
-      case 0: return launch_gemm<T, 128, 128, 2>(M, N, K, ksplit, la, lb, ep, st);
-      case 3: return launch_gemm_ms<128, 128, 2, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
-      default: return launch_gemm_ms<256, 128, 4, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
-    }
-  } else {
-    return launch_gemm<T, 128, 128, 2>(M, N, K, ksplit, la, lb, ep, st);
-  }
-}
-// convolution GEMMs with N >= 128 (and M >= 128): the 8-wave large-tile
-// kernel where both loaders speak the buffer protocol (VLP_GEMM_VARIANT >= 5)
-template <typename T, class LA, class LB, class EP>
-inline int gemm_conv_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
-                          hipStream_t st) {
-  if constexpr (use_bk<T, LA, LB>()) {
-    if (gemm_variant() >= 5) return gemm_big_auto(M, N, K, ksplit, la, lb, ep, st);
-  }
-  return gemm_wide<T>(M, N, K, ksplit, la, lb, ep, st);
-}
-// N <= 64 columns (Co = 64 convs)
-template <typename T, class LA, class LB, class EP>
-inline int gemm_narrow(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
-                       hipStream_t st) {
-  if constexpr (use_bk<T, LA, LB>()) {
-    if (gemm_variant() >= 6 && M >= 512) return launch_gemm_big<512, 64, 8, 1>(M, N, K, ksplit, la, lb, ep, st);
-    if (gemm_variant() >= 4) return launch_gemm_bk<256, 64, 4, 1>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if constexpr (use_ms<T, LA, LB>()) {
-    switch (gemm_variant()) {
-      case 0: return launch_gemm<T, 256, 64, 4>(M, N, K, ksplit, la, lb, ep, st);
-      case 3: return launch_gemm_ms<256, 64, 4, 1, 2>(M, N, K, ksplit, la, lb, ep, st);
-      default: return launch_gemm_ms<256, 64, 4, 1, 4>(M, N, K, ksplit, la, lb, ep, st);
-    }
-  } else {
-    return launch_gemm<T, 256, 64, 4>(M, N, K, ksplit, la, lb, ep, st);
-  }
-}
-// M <= 64 rows (weight gradients of Co = 64 convs)
-template <typename T, class LA, class LB, class EP>
-inline int gemm_short(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
-                      hipStream_t st) {
-  if constexpr (use_bk<T, LA, LB>()) {
-    // 64 x 192 tiles (3 taps of 64 channels) on the two-K-tiles-in-flight engine:
-    // the 4-wave 64 x 128 ring kept one K-tile in flight and was latency-bound
-    constexpr int short_big = 1;
-    if (gemm_variant() >= 5 && short_big && N % 192 == 0)
-      return launch_gemm_big<64, 192, 1, 4>(M, N, K, ksplit, la, lb, ep, st);
-    if (gemm_variant() >= 4) return launch_gemm_bk<64, 128, 1, 4>(M, N, K, ksplit, la, lb, ep, st);
-  }
-  if constexpr (use_ms<T, LA, LB>()) {
-    switch (gemm_variant()) {
-      case 0: return launch_gemm<T, 64, 128, 1>(M, N, K, ksplit, la, lb, ep, st);
-      default: return launch_gemm_ms<64, 128, 1, 4, 2>(M, N, K, ksplit, la, lb, ep, st);
-    }
-  } else {
-    return launch_gemm<T, 64, 128, 1>(M, N, K, ksplit, la, lb, ep, st);
-  }
-}
-
-// Host-side launcher.  ksplit > 1 splits the reduction over grid.y (the
-// epilogue must then accumulate atomically).
+// Host-side launcher of the register-staged gemm_kernel.  ksplit > 1 splits the
+// reduction over grid.y (the epilogue must then accumulate atomically).
 template <typename T, int BM, int BN, int WGM, class LA, class LB, class EP>
 inline int launch_gemm(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
                        hipStream_t stream) {
   constexpr int BK = Elem<T>::BK;
   if (M <= 0 || N <= 0) return 0;
   GemmShape sh;
-  sh.xsplit = 0;
   sh.nsplit = 1;
-  sh.dbg = 0;
   sh.M = M; sh.N = N; sh.K = K;
   sh.tiles_m = (M + BM - 1) / BM;
   sh.tiles_n = (N + BN - 1) / BN;
   if (ksplit <= 0) {   // auto: ~1024 workgroups, >= 4096-deep splits
     const int tiles = sh.tiles_m * sh.tiles_n;
     ksplit = (1024 + tiles - 1) / tiles;
-    const int maxsplit = (K + 4095) / 4096;
-    if (ksplit > maxsplit) ksplit = maxsplit;
+    const int max_split = (K + 4095) / 4096;
+    if (ksplit > max_split) ksplit = max_split;
   }
   if (ksplit < 1) ksplit = 1;
   int kc = (K + ksplit - 1) / ksplit;
@@ -2075,6 +1668,84 @@ inline int launch_gemm(int M, int N, int K, int ksplit, const LA& la, const LB& 
   return (int)hipGetLastError();
 }
 
+// ---------------- dispatch ----------------
+// A bf16 loader pair in which both loaders speak the buffer protocol (use_bk)
+// goes to the LDS-DMA launchers: launch_gemm_bk, launch_gemm_big or
+// launch_gemm_pp, chosen by shape below.  Everything else -- fp32 parity mode,
+// the transforming (XF) convolution loaders, ConvFwdAReg -- goes to the
+// register-staged launch_gemm.
+template <typename T, class LA, class LB>
+constexpr bool use_bk() {
+  return std::is_same<T, bf16>::value && BufTrait<LA>::value && BufTrait<LB>::value;
+}
+// large-tile shape choice: 256x256 (8 waves, one workgroup per CU) when both
+// dimensions allow it, else 128x256, and 128x128 (4 waves) for N = 128
+template <class LA, class LB, class EP>
+inline int gemm_big_auto(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
+  // (256x256 keeps 128x64 fragments per wave live: only the all-K-contig case
+  // fits the 256-VGPR budget without spilling)
+  // ping-pong schedule (gemm_pp_kernel) for K-contig x K-contig and MN x MN
+  // pairs (measured per step: K-contig +0.4-0.8 % (the 256x256 forward /
+  // data-gradient GEMMs +3 %), MN x MN weight gradients another +2.4 % (layers
+  // 3-4 +10-19 %); the 128x256 MN tiles of layer 2 lose (-10 %) and stay on
+  // gemm_big_kernel, as do 256x128 K-contig tiles)
+  constexpr bool kk = LA::kKContig && LB::kKContig;
+  constexpr bool mm = !LA::kKContig && !LB::kKContig;
+  if constexpr (kk || mm) {
+    if (M >= 256 && N >= 256 && K % 64 == 0)
+      return launch_gemm_pp<256, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
+  }
+  if constexpr (mm) {
+    // Co = 128 weight gradients (layer 2, N = 9 * 128 = 3 * 384): 128x384 tiles,
+    // a 64x96 per-wave tile (20 transposing reads per 24 MFMAs)
+    if (M > 64 && M <= 128 && N % 384 == 0 && K % 64 == 0)
+      return launch_gemm_pp<128, 384, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
+  }
+  if constexpr (kk) {
+    if (M >= 256 && N >= 256) return launch_gemm_big<256, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
+  }
+  if (N >= 256) return launch_gemm_big<128, 256, 2, 4>(M, N, K, ksplit, la, lb, ep, st);
+  // N = 128: 128x128 tiles (4 waves, 64 KB ring) run two workgroups per CU, so
+  // one tile's epilogue overlaps the other's main loop (layer 2, K = 1152 is
+  // only 18 K-steps per tile); measured +1 % per step over 256x128
+  return launch_gemm_big<128, 128, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
+}
+// N >= 128 columns
+template <typename T, class LA, class LB, class EP>
+inline int gemm_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+                     hipStream_t st) {
+  if constexpr (use_bk<T, LA, LB>()) return launch_gemm_bk<128, 128, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
+  else return launch_gemm<T, 128, 128, 2>(M, N, K, ksplit, la, lb, ep, st);
+}
+// convolution GEMMs with N >= 128 (and M >= 128): the large-tile kernels
+// where both loaders speak the buffer protocol
+template <typename T, class LA, class LB, class EP>
+inline int gemm_conv_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+                          hipStream_t st) {
+  if constexpr (use_bk<T, LA, LB>()) return gemm_big_auto(M, N, K, ksplit, la, lb, ep, st);
+  else return gemm_wide<T>(M, N, K, ksplit, la, lb, ep, st);
+}
+// N <= 64 columns (Co = 64 convs)
+template <typename T, class LA, class LB, class EP>
+inline int gemm_narrow(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+                       hipStream_t st) {
+  if constexpr (use_bk<T, LA, LB>()) return launch_gemm_bk<256, 64, 4, 1>(M, N, K, ksplit, la, lb, ep, st);
+  else return launch_gemm<T, 256, 64, 4>(M, N, K, ksplit, la, lb, ep, st);
+}
+// M <= 64 rows (weight gradients of Co = 64 convs)
+template <typename T, class LA, class LB, class EP>
+inline int gemm_short(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+                      hipStream_t st) {
+  if constexpr (use_bk<T, LA, LB>()) {
+    // 64 x 192 tiles (3 taps of 64 channels) on the two-K-tiles-in-flight engine:
+    // the 4-wave 64 x 128 ring kept one K-tile in flight and was latency-bound
+    if (N % 192 == 0) return launch_gemm_big<64, 192, 1, 4>(M, N, K, ksplit, la, lb, ep, st);
+    return launch_gemm_bk<64, 128, 1, 4>(M, N, K, ksplit, la, lb, ep, st);
+  } else {
+    return launch_gemm<T, 64, 128, 1>(M, N, K, ksplit, la, lb, ep, st);
+  }
+}
+
 // ---------------- generic loaders ----------------
 // Row-major matrix, K contiguous: A(m,k) = p[m*ld + k].  Zero outside [M) x [K).
 template <typename T>
@@ -2087,6 +1758,7 @@ struct KMat {
   __device__ uint4 load(const State& s, int k) const {
     return (s.ok && k < K) ? ldg16(s.p + k) : zero4();
   }
+  // direct protocol (gemm_kernel's GStager)
   struct DState { const T* p; int kk; bool ok; };
   struct Step {};
   __device__ Step step(int) const { return Step{}; }
@@ -2099,7 +1771,7 @@ struct KMat {
     s.kk += Elem<T>::BK;
     return r;
   }
-  // buffer protocol (gemm_bk_kernel): o = chunk byte offset at k = 0
+  // buffer protocol: o = chunk byte offset at k = 0
   static constexpr bool kBuf = true;
   struct BState { unsigned o; int koff; };
   struct BStep { unsigned kbytes; int klim; };
@@ -2114,25 +1786,13 @@ struct KMat {
 template <typename T>
 struct MNMat {
   static constexpr bool kKContig = false;
-  static constexpr bool kDirect = true;
   struct State { const T* p; bool ok; };
   const T* p; int ld, M, K;
   __device__ State fixed(int m) const { return State{p + m, m < M}; }
   __device__ uint4 load(const State& s, int k) const {
     return (s.ok && k < K) ? ldg16(s.p + (size_t)k * ld) : zero4();
   }
-  struct RState { const T* p; int kk; };   // row k of this thread
-  struct CState { int m; bool ok; };
-  __device__ RState rstart(int k, int kb) const { return RState{p + (size_t)(kb + k) * ld, kb + k}; }
-  __device__ CState cstart(int m) const { return CState{m < M ? m : 0, m < M}; }
-  __device__ const void* addr(const RState& r, const CState& c) const {
-    return (c.ok & (r.kk < K)) ? (const void*)(r.p + c.m) : zero_page();
-  }
-  __device__ void radvance(RState& r) const {
-    r.p += (size_t)Elem<T>::BK * ld;
-    r.kk += Elem<T>::BK;
-  }
-  // buffer protocol (gemm_bk_kernel)
+  // buffer protocol
   static constexpr bool kBuf = true;
   __device__ rsrc_t rsrc() const { return buf_rsrc(p, (unsigned)(((size_t)(K - 1) * ld + M) * sizeof(T))); }
   struct BRow { unsigned o; int kk; };
