@@ -413,6 +413,28 @@ int vlp_nest_rowscale(int dtype, long long M, int N, int rows, const float* s, v
 /* global average pool backward: dy[b*HW + p][c] = dfeat[b][c] * inv */
 int vlp_nest_bcast(int dtype, int B, int HW, int C, const float* dfeat, float inv, void* dy, void* stream);
 
+/* ---------------- ViT image encoder (vit_base_patch16_224, vit_large_patch16_224) ----------------
+ * Replace timm vision_transformer.py's pieces behind timm.create_model(model, ...)
+ * (OnlyImagingModule.py:73; ImageEncoder, VisionLanguageModule.py:30-32).  The blocks run on
+ * vlp_layernorm_* / vlp_linear_* and on the NesT flash-attention kernels at head dim 64.
+ * Attention over B images of N >= 1 tokens: qkv[B*N][3C] rows (q | k | v, head h at h*64),
+ * out[B*N][C] head-major (h*64 + d, timm's own order: no proj-weight permutation),
+ * lse[B*H*N] (log2 domain), head dim 64 only.  Backward: delta[B*H*N] scratch; writes
+ * every column of dqkv.  No atomics: results are bitwise reproducible. */
+int vlp_vit_attn_fwd(int dtype, int B, int H, int N, int dh, const void* qkv, void* out, float* lse,
+                     float scale, void* stream);
+int vlp_vit_attn_bwd(int dtype, int B, int H, int N, int dh, const void* qkv, const void* out,
+                     const void* dout, const float* lse, float* delta, void* dqkv, float scale, void* stream);
+/* patch-embed im2col: 16x16/16 patches -> out[B*(H/16)*(W/16)][768], raster patch order, columns
+ * (c, ky, kx) as patch_embed.proj.weight[D][3][16][16] flattens; H, W multiples of 16; exactly
+ * one of x (fp32 [B][3][H][W], normalised) / x_u8 ([B][1][H][W], (v-mean)/std, channel replicated) */
+int vlp_vit_patch_prep(int dtype, int B, int H, int W, const float* x, const uint8_t* x_u8, float mean,
+                       float std_, void* out, void* stream);
+/* tok[b][0] = cls + pos[0], tok[b][1+p] = patch[b][p] + pos[1+p]: patch[B*(N-1)][D], cls[D] and
+ * pos[N][D] fp32, tok[B*N][D]; D a multiple of the 16-B chunk (8 bf16 / 4 fp32) */
+int vlp_vit_assemble(int dtype, int B, int N, int D, const void* patch, const float* cls, const float* pos,
+                     void* tok, void* stream);
+
 /* ---------------- contrastive head ----------------
  * Replace VisionLanguageModule.forward (VisionLanguageModule.py:441-461: projections,
  * F.normalize, logit_scale.exp().clamp(max=100) * img @ txt.T) and

@@ -1,6 +1,8 @@
 """Flash-attention kernels of the NesT tower at the bs=128, 512x512 level shapes
 (BT = B * blocks, H heads of 32, N = 1024 tokens per block).
-  python tools/nest_attn_bench.py [--levels 0,1,2] [--iters 5]"""
+  python tools/nest_attn_bench.py [--levels 0,1,2] [--iters 5]
+With --dh 64 the same kernels at the ViT head dim (vlp_vit_attn_*); --bh B,H replaces the
+level shapes (e.g. --dh 64 --bh 2,12 --N 197 for ViT-B/16 tokens)."""
 import argparse
 import math
 import os
@@ -31,21 +33,26 @@ def main():
     ap.add_argument("--levels", default="0,1,2")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--N", type=int, default=1024)
+    ap.add_argument("--dh", type=int, default=32, choices=(32, 64))
+    ap.add_argument("--bh", default=None, help="B,H instead of the NesT level shapes")
     a = ap.parse_args()
-    for lv in [int(v) for v in a.levels.split(",")]:
-        BT, H = LEVELS[lv]
-        N, C = a.N, 32 * H
+    dh = a.dh
+    fwd, bwd = (ops.nest_attn_fwd, ops.nest_attn_bwd) if dh == 32 else (ops.vit_attn_fwd, ops.vit_attn_bwd)
+    shapes = ([("shape", tuple(int(v) for v in a.bh.split(",")))] if a.bh
+              else [(f"level {lv}", LEVELS[int(lv)]) for lv in a.levels.split(",")])
+    for tag, (BT, H) in shapes:
+        N, C = a.N, dh * H
         qkv = (torch.randn(BT * N, 3 * C, device="cuda") * 0.5).to(torch.bfloat16)
         out = torch.empty(BT * N, C, dtype=torch.bfloat16, device="cuda")
         lse = torch.empty(BT * H * N, device="cuda")
         do = torch.randn_like(out)
         dqkv = torch.empty_like(qkv)
         delta = torch.empty_like(lse)
-        s = 1 / math.sqrt(32)
-        tf = tm(lambda: ops.nest_attn_fwd(qkv, out, lse, BT, H, N, s), a.iters)
-        tb = tm(lambda: ops.nest_attn_bwd(qkv, out, do, lse, delta, dqkv, BT, H, N, s), a.iters)
-        f = 4.0 * BT * H * N * N * 32
-        print(f"level {lv} BT={BT} H={H} N={N}: fwd {tf:8.1f} us {f / tf / 1e6:6.1f} TF/s | "
+        s = 1 / math.sqrt(dh)
+        tf = tm(lambda: fwd(qkv, out, lse, BT, H, N, s), a.iters)
+        tb = tm(lambda: bwd(qkv, out, do, lse, delta, dqkv, BT, H, N, s), a.iters)
+        f = 4.0 * BT * H * N * N * dh
+        print(f"{tag} dh={dh} BT={BT} H={H} N={N}: fwd {tf:8.1f} us {f / tf / 1e6:6.1f} TF/s | "
               f"bwd {tb:8.1f} us {2.5 * f / tb / 1e6:6.1f} TF/s", flush=True)
 
 

@@ -25,7 +25,8 @@
 
 namespace vlp {
 
-constexpr int kDh = 32;                 // head dim (every NesT variant: C / heads = 32)
+constexpr int kDh = 32;                 // NesT's head dim (every variant: C / heads = 32)
+constexpr int kVitDh = 64;              // ViT-B/16, ViT-L/16: C / heads = 64 (vlp_vit_attn_*)
 constexpr int kTileRows = 64;           // key / query tokens per staged tile
 constexpr int kQBlock = 128;            // queries per forward / dQ workgroup (4 waves x 32)
 
@@ -33,12 +34,22 @@ constexpr int kQBlock = 128;            // queries per forward / dQ workgroup (4
 // Convention as bert_ops.hip: D[m][n] = sum_k X[m][k] Y[n][k]; lane l = 16g + i
 // holds D[4g + r][i].
 //
-// Tiles of 64 tokens x 32 channels are staged in LDS as [token][channel]
-// images.  bf16 images are unpadded 64-B rows whose four 16-B chunks are
-// XOR-swizzled by sw(row) = ((row>>2)&1)<<1 | ((row>>3)&1): the ds_read_b128
-// row read (16 consecutive rows, one chunk) and the ds_read_b64_tr_b16
-// transposed read (rows 4g + q of two groups, two adjacent chunks) are both
-// bank-conflict free on it.  fp32 images are padded rows of 36 floats.
+// The kernels are templates over the head dim DH (32: NesT, 64: ViT).  Tiles of
+// 64 tokens x DH channels are staged in LDS as [token][channel] images.  bf16
+// images are unpadded rows of 2*DH bytes whose 16-B chunks are XOR-swizzled so
+// that the ds_read_b128 row read (16 consecutive rows, one chunk per lane group
+// g) and the ds_read_b64_tr_b16 transposed read (rows 4g + q of two groups, two
+// adjacent chunks) are both bank-conflict free:
+//   DH 32 (64-B rows, 4 rows per 256-B bank row):
+//     sw(row) = ((row>>2)&1)<<1 | ((row>>3)&1)
+//   DH 64 (128-B rows, 2 rows per bank row; 16-B slot = 8*(row&1) + (chunk ^ sw)):
+//     sw(row) = row & 6.  Transposed read: a 32-lane half takes rows 8n .. 8n+7,
+//     chunks c, c+1 (c even); sw is even, so each row's pair stays a pair, and
+//     the four rows of one parity have four different (row>>1)&3: 16 slots.
+//     Row read: a ds_read_b128 group is rows {0-3, 12-15} at chunk c and rows
+//     {4-11} at chunk c^1 (or the reverse), so with row bits b3..b0 its lane's
+//     slot is (b0, c2^b2, c1^b1, [b3 != b2] ^ c0): one-to-one in (b3..b0).
+// fp32 images are padded rows of DH + 4 floats.
 //
 // Score tiles never pass through LDS: an accumulator v4f s[b] (b = 0..3) holds
 // S[key 16b + 4g + r][i] (or S[q 16b + 4g + r][key i] in dK/dV), and the MFMA's
@@ -46,15 +57,17 @@ constexpr int kQBlock = 128;            // queries per forward / dQ workgroup (4
 // accumulators (as bf16) straight to the next product as the operand whose
 // k-slot j of lane group g is token 16(2h + j/4) + 4g + j%4; vtfrag() reads the
 // other operand (a [token][channel] image, channel on the lane) in that order.
-template <typename T> struct FA;
-template <> struct FA<bf16> {
-  static constexpr int KS = 32, IMG = kTileRows * 32;
+template <typename T, int DH> struct FA;
+template <int DH> struct FA<bf16, DH> {
+  static constexpr int KS = 32, IMG = kTileRows * DH;
   typedef v8bf F;
-  __device__ static __forceinline__ int sw(int row) { return (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
-  __device__ static __forceinline__ int at(int row, int col) {
-    return row * 32 + ((((col >> 3) ^ sw(row)) << 3) | (col & 7));
+  __device__ static __forceinline__ int sw(int row) {
+    return DH == 32 ? (((row >> 2) & 1) << 1) | ((row >> 3) & 1) : row & 6;
   }
-  // rows r0 + i, k = k0 + 8g .. +7 of an image (k0 = 0: one k-step spans the 32 channels)
+  __device__ static __forceinline__ int at(int row, int col) {
+    return row * DH + ((((col >> 3) ^ sw(row)) << 3) | (col & 7));
+  }
+  // rows r0 + i, k = k0 + 8g .. +7 of an image (one k-step spans 32 channels)
   __device__ static __forceinline__ F kfrag(const bf16* img, int r0, int k0) {
     const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
     return *reinterpret_cast<const v8bf*>(img + at(r0 + i, k0 + 8 * g));
@@ -93,8 +106,8 @@ template <> struct FA<bf16> {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, y, acc, 0, 0, 0);
   }
 };
-template <> struct FA<float> {
-  static constexpr int KS = 16, LD = 36, IMG = kTileRows * LD;
+template <int DH> struct FA<float, DH> {
+  static constexpr int KS = 16, LD = DH + 4, IMG = kTileRows * LD;
   typedef v4f F;
   __device__ static __forceinline__ int at(int row, int col) { return row * LD + col; }
   __device__ static __forceinline__ F kfrag(const float* img, int r0, int k0) {
@@ -170,7 +183,7 @@ template <> __device__ __forceinline__ void st4<float>(float* p, float a, float 
 }
 
 // Register-staged tile copy (issue the global loads early, write the LDS
-// image after the barrier): rows [t0, t0+64) x 32 channels at column `col` of a
+// image after the barrier): rows [t0, t0+64) x DH channels at column `col` of a
 // [rows][ld] tensor; rows >= N are zero in the image.  The loads are
 // unconditional (row index clamped to N-1); the store applies the row mask.
 // 256 threads.  The loads are inline asm, waited for by hand at the bottom of the
@@ -212,9 +225,9 @@ template <class X>
 __device__ __forceinline__ void launder(X& x) {
   asm volatile("" : "+v"(x));
 }
-template <typename T>
+template <typename T, int DH>
 struct TileStage {
-  static constexpr int EPC = 16 / (int)sizeof(T), CPR = kDh / EPC, CPT = kTileRows * CPR / 256;
+  static constexpr int EPC = 16 / (int)sizeof(T), CPR = DH / EPC, CPT = kTileRows * CPR / 256;
   u32x4 v[CPT];
   __device__ __forceinline__ void load(const T* src, size_t ld, int col, int t0, int N) {
 #pragma unroll
@@ -234,7 +247,7 @@ struct TileStage {
     for (int c = 0; c < CPT; ++c) {
       const int q = threadIdx.x + 256 * c, r = q / CPR, ch = q % CPR;
       const u32x4 z = {0u, 0u, 0u, 0u};
-      *reinterpret_cast<u32x4*>(img + FA<T>::at(r, ch * EPC)) = t0 + r < N ? v[c] : z;
+      *reinterpret_cast<u32x4*>(img + FA<T, DH>::at(r, ch * EPC)) = t0 + r < N ? v[c] : z;
     }
   }
 };
@@ -267,22 +280,22 @@ __device__ __forceinline__ void attn_tile(int nx, int H, int& x, int& h, int& bt
 // ---------------- forward ----------------
 // grid (ceil(N/128), H, BT); 4 waves, wave w owns queries qt*128 + 32w .. +31
 // as two 16-query subtiles that share every K / V fragment read.
-// out[bt*N + q][h*32 + d]; lse[(bt*H + h)*N + q] = log2-sum-exp of the scaled
+// out[bt*N + q][h*DH + d]; lse[(bt*H + h)*N + q] = log2-sum-exp of the scaled
 // (x log2 e) scores.  Per key tile: S^T = K Q^T, the online softmax in
 // registers (lane = query, 16 keys per lane), O^T += V^T P^T with P fed from
 // the accumulators; the row sums come out of the same product with a ones
 // operand (1^T P^T), i.e. they sum exactly the weights O accumulates.
-template <typename T>
+template <typename T, int DH>
 __global__ void __launch_bounds__(256)
 nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restrict__ out,
                      float* __restrict__ lse, float sl2) {
-  using M = FA<T>;
-  constexpr int QW = 2, KSN = kDh / M::KS;
+  using M = FA<T, DH>;
+  constexpr int QW = 2, KSN = DH / M::KS;
   __shared__ __attribute__((aligned(16))) T sK[M::IMG];
   __shared__ __attribute__((aligned(16))) T sV[M::IMG];
   int qt, h, bt;
   attn_tile((N + kQBlock - 1) / kQBlock, H, qt, h, bt);
-  const int C = H * kDh;
+  const int C = H * DH;
   const size_t ld3 = 3 * (size_t)C;
   const T* base = qkv + (size_t)bt * N * ld3;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
@@ -292,23 +305,26 @@ nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restr
   for (int u = 0; u < QW; ++u)
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks)
-      qf[u][ks] = M::gfrag(base + h * kDh, ld3, q0 + 16 * u, ks * M::KS, q0 + 16 * u + li < N);
+      qf[u][ks] = M::gfrag(base + h * DH, ld3, q0 + 16 * u, ks * M::KS, q0 + 16 * u + li < N);
   const typename M::F one = M::ones();
   float mi[QW];
-  v4f o[QW][2], lsum[QW];
+  constexpr int DB = DH / 16;   // 16-channel accumulator blocks
+  v4f o[QW][DB], lsum[QW];
 #pragma unroll
   for (int u = 0; u < QW; ++u) {
     mi[u] = -INFINITY;
-    lsum[u] = o[u][0] = o[u][1] = v4f{0.f, 0.f, 0.f, 0.f};
+    lsum[u] = v4f{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int db = 0; db < DB; ++db) o[u][db] = v4f{0.f, 0.f, 0.f, 0.f};
   }
   const int nt = (N + kTileRows - 1) / kTileRows;
 #pragma unroll
   for (int u = 0; u < QW; ++u)
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks) launder(qf[u][ks]);
-  TileStage<T> stk, stv;
-  stk.load(base, ld3, C + h * kDh, 0, N);
-  stv.load(base, ld3, 2 * C + h * kDh, 0, N);
+  TileStage<T, DH> stk, stv;
+  stk.load(base, ld3, C + h * DH, 0, N);
+  stv.load(base, ld3, 2 * C + h * DH, 0, N);
   stk.wait();
   stv.wait();
   for (int t = 0; t < nt; ++t) {
@@ -319,8 +335,8 @@ nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restr
     // next tile's loads fly under this tile's MFMAs (unconditional: past the
     // end they re-read row N-1, which keeps the loaded registers phi-free so
     // nothing waits on them before the next store)
-    stk.load(base, ld3, C + h * kDh, (t + 1) * kTileRows, N);
-    stv.load(base, ld3, 2 * C + h * kDh, (t + 1) * kTileRows, N);
+    stk.load(base, ld3, C + h * DH, (t + 1) * kTileRows, N);
+    stv.load(base, ld3, 2 * C + h * DH, (t + 1) * kTileRows, N);
     v4f s[QW][4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -351,19 +367,21 @@ nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restr
 #pragma unroll
         for (int r = 0; r < 4; ++r) s[u][b][r] = exp2_hw(fmaf(s[u][b][r], sl2, -mn));
       mi[u] = mn;
-      o[u][0] *= alpha;
-      o[u][1] *= alpha;
+#pragma unroll
+      for (int db = 0; db < DB; ++db) o[u][db] *= alpha;
       lsum[u] *= alpha;
     }
     // O^T[d][q] += sum_key V^T[d][key] P[q][key];  l[q] += sum_key P[q][key]
 #pragma unroll
     for (int hs = 0; hs < kTileRows / M::KS; ++hs) {
-      const typename M::F v0 = M::vtfrag(sV, hs * M::KS, 0), v1 = M::vtfrag(sV, hs * M::KS, 16);
+      typename M::F vt[DB];
+#pragma unroll
+      for (int db = 0; db < DB; ++db) vt[db] = M::vtfrag(sV, hs * M::KS, 16 * db);
 #pragma unroll
       for (int u = 0; u < QW; ++u) {
         const typename M::F pf = M::pfrag(s[u], hs);
-        M::mma(o[u][0], v0, pf);
-        M::mma(o[u][1], v1, pf);
+#pragma unroll
+        for (int db = 0; db < DB; ++db) M::mma(o[u][db], vt[db], pf);
         M::mma(lsum[u], one, pf);
       }
     }
@@ -375,9 +393,9 @@ nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restr
     const int q = q0 + 16 * u + li;
     if (q < N) {
       const float inv = 1.f / lsum[u][0];
-      T* dst = out + ((size_t)bt * N + q) * C + h * kDh;
+      T* dst = out + ((size_t)bt * N + q) * C + h * DH;
 #pragma unroll
-      for (int db = 0; db < 2; ++db)
+      for (int db = 0; db < DB; ++db)
         st4<T>(dst + 16 * db + 4 * lg, o[u][db][0] * inv, o[u][db][1] * inv, o[u][db][2] * inv,
                o[u][db][3] * inv);
       if (lg == 0) lse[((size_t)bt * H + h) * N + q] = mi[u] + log2f(lsum[u][0]);
@@ -385,9 +403,10 @@ nest_attn_fwd_kernel(int BT, int H, int N, const T* __restrict__ qkv, T* __restr
   }
 }
 
-// delta[(bt*H + h)*N + q] = sum_d dout[row][h*32 + d] * out[row][h*32 + d]
-template <typename T>
-__global__ void nest_attn_delta_kernel(int BT, int H, int N, const T* __restrict__ out,
+// delta[(bt*H + h)*N + q] = sum_d dout[row][h*DH + d] * out[row][h*DH + d]
+template <typename T, int DH>
+__global__ void __launch_bounds__(256)
+nest_attn_delta_kernel(int BT, int H, int N, const T* __restrict__ out,
                                        const T* __restrict__ dout, float* __restrict__ delta) {
   constexpr int EPC = 16 / (int)sizeof(T);
   const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;   // (row, h)
@@ -395,12 +414,12 @@ __global__ void nest_attn_delta_kernel(int BT, int H, int N, const T* __restrict
   if (idx >= total) return;
   const size_t row = idx / H;
   const int h = (int)(idx - row * H);
-  const int C = H * kDh;
-  const T* a = out + row * C + h * kDh;
-  const T* b = dout + row * C + h * kDh;
+  const int C = H * DH;
+  const T* a = out + row * C + h * DH;
+  const T* b = dout + row * C + h * DH;
   float s = 0.f;
 #pragma unroll
-  for (int c = 0; c < kDh; c += EPC) {
+  for (int c = 0; c < DH; c += EPC) {
     float x[EPC], y[EPC];
     Chunk<T>::unpack(ldg16(a + c), x);
     Chunk<T>::unpack(ldg16(b + c), y);
@@ -416,18 +435,18 @@ __global__ void nest_attn_delta_kernel(int BT, int H, int N, const T* __restrict
 // 16-query subtiles (lane = query) sharing the K / V fragment reads.
 //   P = exp2(S*sl2 - lse), dP' = dO V^T - delta (the accumulator starts at
 //   -delta), dS = P dP', dQ^T += K^T dS^T with dS fed from the accumulators.
-template <typename T>
+template <typename T, int DH>
 __global__ void __launch_bounds__(256)
 nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T* __restrict__ dout,
                         const float* __restrict__ lse, const float* __restrict__ delta, T* __restrict__ dqkv,
                         float sl2, float scale) {
-  using M = FA<T>;
-  constexpr int QW = 2, KSN = kDh / M::KS;
+  using M = FA<T, DH>;
+  constexpr int QW = 2, KSN = DH / M::KS;
   __shared__ __attribute__((aligned(16))) T sK[M::IMG];
   __shared__ __attribute__((aligned(16))) T sV[M::IMG];
   int qt, h, bt;
   attn_tile((N + kQBlock - 1) / kQBlock, H, qt, h, bt);
-  const int C = H * kDh;
+  const int C = H * DH;
   const size_t ld3 = 3 * (size_t)C;
   const T* base = qkv + (size_t)bt * N * ld3;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, li = l & 15, lg = l >> 4;
@@ -440,16 +459,19 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
     const bool ok = q + li < N;
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks) {
-      qf[u][ks] = M::gfrag(base + h * kDh, ld3, q, ks * M::KS, ok);
-      df[u][ks] = M::gfrag(dout + (size_t)bt * N * C + h * kDh, C, q, ks * M::KS, ok);
+      qf[u][ks] = M::gfrag(base + h * DH, ld3, q, ks * M::KS, ok);
+      df[u][ks] = M::gfrag(dout + (size_t)bt * N * C + h * DH, C, q, ks * M::KS, ok);
     }
     const size_t so = ((size_t)bt * H + h) * N + q + li;
     lq[u] = ok ? lse[so] : INFINITY;
     ndl[u] = ok ? -delta[so] : 0.f;
   }
-  v4f acc[QW][2];
+  constexpr int DB = DH / 16;
+  v4f acc[QW][DB];
 #pragma unroll
-  for (int u = 0; u < QW; ++u) acc[u][0] = acc[u][1] = v4f{0.f, 0.f, 0.f, 0.f};
+  for (int u = 0; u < QW; ++u)
+#pragma unroll
+    for (int db = 0; db < DB; ++db) acc[u][db] = v4f{0.f, 0.f, 0.f, 0.f};
   const int nt = (N + kTileRows - 1) / kTileRows;
 #pragma unroll
   for (int u = 0; u < QW; ++u) {
@@ -461,9 +483,9 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
     launder(lq[u]);
     launder(ndl[u]);
   }
-  TileStage<T> stk, stv;
-  stk.load(base, ld3, C + h * kDh, 0, N);
-  stv.load(base, ld3, 2 * C + h * kDh, 0, N);
+  TileStage<T, DH> stk, stv;
+  stk.load(base, ld3, C + h * DH, 0, N);
+  stv.load(base, ld3, 2 * C + h * DH, 0, N);
   stk.wait();
   stv.wait();
   for (int t = 0; t < nt; ++t) {
@@ -471,8 +493,8 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
     stk.store(sK, t * kTileRows, N);
     stv.store(sV, t * kTileRows, N);
     __syncthreads();
-    stk.load(base, ld3, C + h * kDh, (t + 1) * kTileRows, N);
-    stv.load(base, ld3, 2 * C + h * kDh, (t + 1) * kTileRows, N);
+    stk.load(base, ld3, C + h * DH, (t + 1) * kTileRows, N);
+    stv.load(base, ld3, 2 * C + h * DH, (t + 1) * kTileRows, N);
     v4f ds[QW][4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -508,12 +530,14 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
     // dQ^T[d][q] += sum_key K^T[d][key] dS[q][key]
 #pragma unroll
     for (int hs = 0; hs < kTileRows / M::KS; ++hs) {
-      const typename M::F k0 = M::vtfrag(sK, hs * M::KS, 0), k1 = M::vtfrag(sK, hs * M::KS, 16);
+      typename M::F kt[DB];
+#pragma unroll
+      for (int db = 0; db < DB; ++db) kt[db] = M::vtfrag(sK, hs * M::KS, 16 * db);
 #pragma unroll
       for (int u = 0; u < QW; ++u) {
         const typename M::F pf = M::pfrag(ds[u], hs);
-        M::mma(acc[u][0], k0, pf);
-        M::mma(acc[u][1], k1, pf);
+#pragma unroll
+        for (int db = 0; db < DB; ++db) M::mma(acc[u][db], kt[db], pf);
       }
     }
     stk.wait();
@@ -523,9 +547,9 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
   for (int u = 0; u < QW; ++u) {
     const int q = q0 + 16 * u + li;
     if (q < N) {
-      T* dst = dqkv + ((size_t)bt * N + q) * ld3 + h * kDh;
+      T* dst = dqkv + ((size_t)bt * N + q) * ld3 + h * DH;
 #pragma unroll
-      for (int db = 0; db < 2; ++db)
+      for (int db = 0; db < DB; ++db)
         st4<T>(dst + 16 * db + 4 * lg, acc[u][db][0] * scale, acc[u][db][1] * scale, acc[u][db][2] * scale,
                acc[u][db][3] * scale);
     }
@@ -539,19 +563,19 @@ nest_attn_bwd_dq_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T
 //   16b + 4g + r), P and dS from them, then dV^T += dO^T P and dK^T += Q^T dS
 //   with P / dS fed from the accumulators.  Query rows >= N are zero in the
 //   images with lse = +inf, so they carry no probability.
-template <typename T>
+template <typename T, int DH>
 __global__ void __launch_bounds__(256)
 nest_attn_bwd_dkdv_kernel(int BT, int H, int N, const T* __restrict__ qkv, const T* __restrict__ dout,
                           const float* __restrict__ lse, const float* __restrict__ delta,
                           T* __restrict__ dqkv, float sl2, float scale) {
-  using M = FA<T>;
-  constexpr int KW = 1, KSN = kDh / M::KS;
+  using M = FA<T, DH>;
+  constexpr int KW = 1, KSN = DH / M::KS;
   __shared__ __attribute__((aligned(16))) T sQ[M::IMG];
   __shared__ __attribute__((aligned(16))) T sD[M::IMG];
   __shared__ __attribute__((aligned(16))) float sL[kTileRows], sDl[kTileRows];
   int kt, h, bt;
   attn_tile((N + 63) / 64, H, kt, h, bt);
-  const int C = H * kDh;
+  const int C = H * DH;
   const size_t ld3 = 3 * (size_t)C;
   const T* base = qkv + (size_t)bt * N * ld3;
   const T* dbase = dout + (size_t)bt * N * C;
@@ -563,12 +587,15 @@ nest_attn_bwd_dkdv_kernel(int BT, int H, int N, const T* __restrict__ qkv, const
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks) {
       const bool ok = k0 + 16 * u + li < N;
-      kf[u][ks] = M::gfrag(base + C + h * kDh, ld3, k0 + 16 * u, ks * M::KS, ok);
-      vf[u][ks] = M::gfrag(base + 2 * C + h * kDh, ld3, k0 + 16 * u, ks * M::KS, ok);
+      kf[u][ks] = M::gfrag(base + C + h * DH, ld3, k0 + 16 * u, ks * M::KS, ok);
+      vf[u][ks] = M::gfrag(base + 2 * C + h * DH, ld3, k0 + 16 * u, ks * M::KS, ok);
     }
-  v4f dk[KW][2], dv[KW][2];
+  constexpr int DB = DH / 16;
+  v4f dk[KW][DB], dv[KW][DB];
 #pragma unroll
-  for (int u = 0; u < KW; ++u) dk[u][0] = dk[u][1] = dv[u][0] = dv[u][1] = v4f{0.f, 0.f, 0.f, 0.f};
+  for (int u = 0; u < KW; ++u)
+#pragma unroll
+    for (int db = 0; db < DB; ++db) dk[u][db] = dv[u][db] = v4f{0.f, 0.f, 0.f, 0.f};
   const size_t sb = ((size_t)bt * H + h) * N;
   const int nt = (N + kTileRows - 1) / kTileRows;
 #pragma unroll
@@ -578,11 +605,11 @@ nest_attn_bwd_dkdv_kernel(int BT, int H, int N, const T* __restrict__ qkv, const
       launder(kf[u][ks]);
       launder(vf[u][ks]);
     }
-  TileStage<T> stq, std_;
+  TileStage<T, DH> stq, std_;
   float pl = 0.f, pd = 0.f;
   auto load_rows = [&](int t0) {
-    stq.load(base, ld3, h * kDh, t0, N);
-    std_.load(dbase, C, h * kDh, t0, N);
+    stq.load(base, ld3, h * DH, t0, N);
+    std_.load(dbase, C, h * DH, t0, N);
     const int q = min(t0 + (int)(threadIdx.x & (kTileRows - 1)), N - 1);   // every thread: no phi
     pl = ldg4_issue(lse + sb + q);
     pd = ldg4_issue(delta + sb + q);
@@ -637,7 +664,7 @@ nest_attn_bwd_dkdv_kernel(int BT, int H, int N, const T* __restrict__ qkv, const
 #pragma unroll
     for (int hs = 0; hs < kTileRows / M::KS; ++hs)
 #pragma unroll
-      for (int db = 0; db < 2; ++db) {
+      for (int db = 0; db < DB; ++db) {
         const typename M::F dt = M::vtfrag(sD, hs * M::KS, 16 * db), qt_ = M::vtfrag(sQ, hs * M::KS, 16 * db);
 #pragma unroll
         for (int u = 0; u < KW; ++u) {
@@ -651,9 +678,9 @@ nest_attn_bwd_dkdv_kernel(int BT, int H, int N, const T* __restrict__ qkv, const
   for (int u = 0; u < KW; ++u) {
     const int key = k0 + 16 * u + li;
     if (key < N) {
-      T* dst = dqkv + ((size_t)bt * N + key) * ld3 + h * kDh;
+      T* dst = dqkv + ((size_t)bt * N + key) * ld3 + h * DH;
 #pragma unroll
-      for (int db = 0; db < 2; ++db) {
+      for (int db = 0; db < DB; ++db) {
         st4<T>(dst + C + 16 * db + 4 * lg, dk[u][db][0] * scale, dk[u][db][1] * scale, dk[u][db][2] * scale,
                dk[u][db][3] * scale);
         st4<T>(dst + 2 * C + 16 * db + 4 * lg, dv[u][db][0], dv[u][db][1], dv[u][db][2], dv[u][db][3]);
@@ -868,39 +895,63 @@ using namespace vlp;
     else F<float>(__VA_ARGS__);                 \
   } while (0)
 
-template <typename T>
+template <typename T, int DH>
 static void attn_fwd_t(int BT, int H, int N, const void* qkv, void* out, float* lse, float scale, hipStream_t st) {
-  hipLaunchKernelGGL(nest_attn_fwd_kernel<T>, dim3(((N + kQBlock - 1) / kQBlock) * H * BT), dim3(256), 0, st, BT, H, N,
-                     (const T*)qkv, (T*)out, lse, scale * 1.4426950408889634f);
+  hipLaunchKernelGGL((nest_attn_fwd_kernel<T, DH>), dim3(((N + kQBlock - 1) / kQBlock) * H * BT), dim3(256), 0, st, BT,
+                     H, N, (const T*)qkv, (T*)out, lse, scale * 1.4426950408889634f);
+}
+template <int DH>
+static int attn_fwd_dh(int dtype, int BT, int H, int N, const void* qkv, void* out, float* lse, float scale,
+                       void* stream) {
+  if (BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (dtype == VLP_BF16) attn_fwd_t<bf16, DH>(BT, H, N, qkv, out, lse, scale, (hipStream_t)stream);
+  else attn_fwd_t<float, DH>(BT, H, N, qkv, out, lse, scale, (hipStream_t)stream);
+  return (int)hipGetLastError();
 }
 VLP_EXPORT int vlp_nest_attn_fwd(int dtype, int BT, int H, int N, int dh, const void* qkv, void* out, float* lse,
                                  float scale, void* stream) {
-  if (dh != kDh || BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31))
-    return (int)hipErrorInvalidValue;
-  NEST_DT(dtype, attn_fwd_t, BT, H, N, qkv, out, lse, scale, (hipStream_t)stream);
-  return (int)hipGetLastError();
+  if (dh != kDh) return (int)hipErrorInvalidValue;
+  return attn_fwd_dh<kDh>(dtype, BT, H, N, qkv, out, lse, scale, stream);
+}
+// the same kernels at head dim 64 (ViT-B/16, ViT-L/16: B images of N = patches + 1 tokens)
+VLP_EXPORT int vlp_vit_attn_fwd(int dtype, int B, int H, int N, int dh, const void* qkv, void* out, float* lse,
+                                float scale, void* stream) {
+  if (dh != kVitDh) return (int)hipErrorInvalidValue;
+  return attn_fwd_dh<kVitDh>(dtype, B, H, N, qkv, out, lse, scale, stream);
 }
 
-template <typename T>
+template <typename T, int DH>
 static void attn_bwd_t(int BT, int H, int N, const void* qkv, const void* out, const void* dout, const float* lse,
                        float* delta, void* dqkv, float scale, hipStream_t st) {
   const size_t rows = (size_t)BT * N * H;
-  hipLaunchKernelGGL(nest_attn_delta_kernel<T>, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, BT, H, N,
+  hipLaunchKernelGGL((nest_attn_delta_kernel<T, DH>), dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, BT, H, N,
                      (const T*)out, (const T*)dout, delta);
   const dim3 gq(((N + kQBlock - 1) / kQBlock) * H * BT), gk(((N + 63) / 64) * H * BT);
   const float sl2 = scale * 1.4426950408889634f;
-  hipLaunchKernelGGL(nest_attn_bwd_dq_kernel<T>, gq, dim3(256), 0, st, BT, H, N, (const T*)qkv, (const T*)dout, lse,
-                     (const float*)delta, (T*)dqkv, sl2, scale);
-  hipLaunchKernelGGL(nest_attn_bwd_dkdv_kernel<T>, gk, dim3(256), 0, st, BT, H, N, (const T*)qkv, (const T*)dout, lse,
-                     (const float*)delta, (T*)dqkv, sl2, scale);
+  hipLaunchKernelGGL((nest_attn_bwd_dq_kernel<T, DH>), gq, dim3(256), 0, st, BT, H, N, (const T*)qkv, (const T*)dout,
+                     lse, (const float*)delta, (T*)dqkv, sl2, scale);
+  hipLaunchKernelGGL((nest_attn_bwd_dkdv_kernel<T, DH>), gk, dim3(256), 0, st, BT, H, N, (const T*)qkv,
+                     (const T*)dout, lse, (const float*)delta, (T*)dqkv, sl2, scale);
+}
+template <int DH>
+static int attn_bwd_dh(int dtype, int BT, int H, int N, const void* qkv, const void* out, const void* dout,
+                       const float* lse, float* delta, void* dqkv, float scale, void* stream) {
+  if (BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (dtype == VLP_BF16) attn_bwd_t<bf16, DH>(BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, (hipStream_t)stream);
+  else attn_bwd_t<float, DH>(BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, (hipStream_t)stream);
+  return (int)hipGetLastError();
 }
 VLP_EXPORT int vlp_nest_attn_bwd(int dtype, int BT, int H, int N, int dh, const void* qkv, const void* out,
                                  const void* dout, const float* lse, float* delta, void* dqkv, float scale,
                                  void* stream) {
-  if (dh != kDh || BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31))
-    return (int)hipErrorInvalidValue;
-  NEST_DT(dtype, attn_bwd_t, BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, (hipStream_t)stream);
-  return (int)hipGetLastError();
+  if (dh != kDh) return (int)hipErrorInvalidValue;
+  return attn_bwd_dh<kDh>(dtype, BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, stream);
+}
+VLP_EXPORT int vlp_vit_attn_bwd(int dtype, int B, int H, int N, int dh, const void* qkv, const void* out,
+                                const void* dout, const float* lse, float* delta, void* dqkv, float scale,
+                                void* stream) {
+  if (dh != kVitDh) return (int)hipErrorInvalidValue;
+  return attn_bwd_dh<kVitDh>(dtype, B, H, N, qkv, out, dout, lse, delta, dqkv, scale, stream);
 }
 
 template <typename T>

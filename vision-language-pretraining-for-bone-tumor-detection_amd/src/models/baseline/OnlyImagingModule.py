@@ -21,8 +21,10 @@ The networks:
   * nest_small: `NestClassifier` (timm nest_small(num_classes=1) on the HIP NesT
     tower, vlp_amd/nest.py; `image_size` sets timm's img_size, default 224 as
     timm's), features [B, 384, 1, 1] after the final LayerNorm and token mean.
-Not built (NotImplementedError): vit_base/large_patch16_224, resnet50 and the
-torchxrayvision resnet50-res512-all backbone.  Checkpoints of a pretrained
+Not built (NotImplementedError): resnet50 and the torchxrayvision
+resnet50-res512-all backbone.  vit_base/large_patch16_224 raise NotImplementedError
+here as well: the tower and a ready `ViTClassifier` exist (vlp_amd/vit.py, used by
+the pretraining ImageEncoder) but are not wired into this module yet.  Checkpoints of a pretrained
 VisionLanguageModule load with torch.load(weights_only=True) (the reference uses
 weights_only=False, :76).
 

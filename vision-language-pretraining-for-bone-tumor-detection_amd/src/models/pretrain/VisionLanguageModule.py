@@ -40,6 +40,7 @@ from vlp_amd.clip_model import ClipHead, ClipStepFn, _project_normalize, role_we
 from vlp_amd.optim import FusedAdamW  # noqa: E402
 from vlp_amd.nest import NEST_CFGS, NestTower  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
+from vlp_amd.vit import VIT_CFGS, ViTTower  # noqa: E402
 from vlp_amd.distilbert import DistilBertConfig, DistilBertTower  # noqa: E402
 from vlp_amd.tinybert import TinyBertConfig, TinyBertTower  # noqa: E402
 
@@ -88,7 +89,7 @@ def _default_device(device):
 
 class ImageEncoder(nn.Module):
     """:27-35 — `timm.create_model(model, pretrained=False, num_classes=0,
-    global_pool="avg", **kwargs)`; here the MI355X ResNet34 tower."""
+    global_pool="avg", **kwargs)`; here the MI355X ResNet34, NesT or ViT tower."""
 
     def __init__(self, model, compute_dtype="fp32", device=None, **kwargs):
         super().__init__()
@@ -102,9 +103,15 @@ class ImageEncoder(nn.Module):
                                    drop_rate=kwargs.get("drop_rate", 0.0),
                                    drop_path_rate=kwargs.get("drop_path_rate", 0.5), compute_dtype=compute_dtype,
                                    device=device)
+        elif model in VIT_CFGS:
+            # timm vision_transformer with num_classes=0, global_pool="avg": the mean of the
+            # patch tokens through fc_norm; img_size as for NesT (timm's default 224)
+            self.model = ViTTower(model, img_size=kwargs.get("img_size", 224),
+                                  drop_rate=kwargs.get("drop_rate", 0.0), compute_dtype=compute_dtype,
+                                  device=device, global_pool="avg", depth=kwargs.get("depth"))
         else:
             raise ValueError(f"ImageEncoder: model {model} is not built for MI355X "
-                             f"(supported: resnet34, {', '.join(NEST_CFGS)})")
+                             f"(supported: resnet34, {', '.join(NEST_CFGS)}, {', '.join(VIT_CFGS)})")
 
     def forward(self, x):
         return self.model(x)
@@ -298,6 +305,8 @@ class VisionLanguageModule(_Base):
             enc_kw["img_size"] = kwargs["image_size"]
         if "drop_path_rate" in kwargs:
             enc_kw["drop_path_rate"] = kwargs["drop_path_rate"]
+        if "image_depth" in kwargs:         # fewer ViT blocks than the variant's (short test towers)
+            enc_kw["depth"] = kwargs["image_depth"]
         self.image_encoder = ImageEncoder(image_model, compute_dtype=compute_dtype, device=dev, **enc_kw)
         feat_dim = self.image_encoder.model.num_features if image_model != "resnet34" else 512
         text_dim = TEXT_HIDDEN.get(text_encoder_model)   # unknown names: TextEncoder's ValueError below

@@ -713,6 +713,28 @@ def layernorm_bwd_add(dy, x, mean, rstd, gamma, addend, dx, dgamma, dbeta, M, D,
                                        ptr(dbeta), _s())
 
 
+# ---------------- ViT image encoder (csrc/vit_ops.hip; attention: csrc/nest_ops.hip at head dim 64) ----------------
+def vit_attn_fwd(qkv, out, lse, B, H, N, scale):
+    tk = ktimer.begin("vit_attn_fwd", 4.0 * B * H * N * N * 64)
+    lib().vlp_vit_attn_fwd(dcode(qkv), B, H, N, 64, ptr(qkv), ptr(out), ptr(lse), float(scale), _s())
+    ktimer.end(tk)
+
+
+def vit_attn_bwd(qkv, out, dout, lse, delta, dqkv, B, H, N, scale):
+    tk = ktimer.begin("vit_attn_bwd", 10.0 * B * H * N * N * 64)
+    lib().vlp_vit_attn_bwd(dcode(qkv), B, H, N, 64, ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(delta),
+                           ptr(dqkv), float(scale), _s())
+    ktimer.end(tk)
+
+
+def vit_patch_prep(out, B, H, W, x=None, x_u8=None, mean=0.0, std=1.0):
+    lib().vlp_vit_patch_prep(dcode(out), B, H, W, ptr(x), ptr(x_u8), float(mean), float(std), ptr(out), _s())
+
+
+def vit_assemble(patch, cls, pos, tok, B, N, D):
+    lib().vlp_vit_assemble(dcode(tok), B, N, D, ptr(patch), ptr(cls), ptr(pos), ptr(tok), _s())
+
+
 # ---------------- radiograph preprocessing / augmentation (csrc/prep_ops.hip) ----------------
 PREP_WORK_BYTES_PER_IMAGE = (64 * 2 + 256 + 2) * 4
 
