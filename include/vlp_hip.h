@@ -465,10 +465,30 @@ int vlp_clip_loss_fused(int B, int N, int E, int offset, const float* img_all,
                         float* g_txt_all, float* d_logit_scale, float* loss_parts,
                         float* lse_out, const float* role_w, float* ws, long long ws_floats,
                         void* stream);
+/* vlp_clip_loss_fused with duplicate-caption negatives masked out (the global batch of a
+ * data-parallel job holds captions more than once; the reference's sampler rules that out
+ * per process only, and its own masked / deduplicate branches of _compute_loss,
+ * VisionLanguageModule.py:506-530 / :532-554, are retired).  cid_all: [N] device ints, one
+ * caption id per gathered row.  An entry (i, j), i != j, with cid_all[i] == cid_all[j] is
+ * left out of both softmaxes as if its logit were -inf (not the retired logits * mask, which
+ * keeps exp(0) in the denominator): nothing in either log-sum-exp, zero gradient, no part in
+ * d_logit_scale; the diagonal always stays, and a row left with its diagonal alone gives
+ * exactly 0 loss and 0 gradient.  Losses stay means over all N rows / columns.  Same
+ * workspace (vlp_clip_loss_ws_floats), outputs and role_w as vlp_clip_loss_fused, and with
+ * all ids distinct the same bits. */
+int vlp_clip_loss_fused_masked(int B, int N, int E, int offset, const float* img_all,
+                               const float* txt_all, const float* logit_scale, const int* cid_all,
+                               float* g_img_all, float* g_txt_all, float* d_logit_scale,
+                               float* loss_parts, float* lse_out, const float* role_w, float* ws,
+                               long long ws_floats, void* stream);
 /* symmetric CE over explicit logits [B][B]: out = {loss, image_loss, text_loss} (+=);
  * dlogits (+=, optional) = d (role_w[0] image_loss + role_w[1] text_loss) / 2 / d logits
  * (role_w NULL: {1, 1}, the reference's loss, :550-552) */
 int vlp_ce_sym(int B, const float* logits, float* out, float* dlogits, const float* role_w, void* stream);
+/* vlp_ce_sym under vlp_clip_loss_fused_masked's rule: cid [B] device ints, entries (i, j),
+ * i != j, with cid[i] == cid[j] are left out of both softmaxes and get no gradient */
+int vlp_ce_sym_masked(int B, const float* logits, const int* cid, float* out, float* dlogits,
+                      const float* role_w, void* stream);
 /* C[M][N] (=|+=) alpha * sum_k A(m,k) B(n,k) on MFMA; a_kc / b_kc: K-contiguous
  * operand ([rows][ld]) else MN-contiguous ([K][ld]).  Every contiguous extent and
  * leading dimension a multiple of 16 B (4 fp32 / 8 bf16), N and ldc multiples of 4;

@@ -27,6 +27,15 @@
 //                    parts and d logit_scale.
 // No atomics: the result is bitwise reproducible run to run.  The owner's
 // rows of the gathered gradients are then reduce-scattered by the host (RCCL).
+// `vlp_clip_loss_fused_masked` (template flag MASK of launches 1 and 2) takes one
+// caption id per gathered row and drops every duplicate-caption negative -- an
+// entry (i, j), i != j, with cid[i] == cid[j] -- from both softmaxes, as if its
+// logit were -inf: it enters neither the running max nor the sum of launch 1,
+// its weight W is 0 in launch 2, and launch 3, which only reads W, runs unchanged.
+// A 64-key tile whose keys are all dropped for a query leaves the neutral partial
+// (max -inf, sum 0) that the tiles past N already leave; the fold skips it.  A
+// query whose every other key is dropped keeps its diagonal alone: its loss term
+// and all its weights are written as exact zeros.
 // MFMA operand convention (as in gemm.h): mfma(a, b, acc) with lane l = 16g + x
 // supplying a[x][k(g)] and b[y = x][k(g)] leaves acc[r] = sum_k a[4g + r][k] b[l & 15][k].
 #include "gemm.h"
@@ -74,11 +83,11 @@ __device__ __forceinline__ v4f ld_row4(const float* base, int row, int rows, int
 // Launch 1.  Wave w: keys k0 = kc * 256 + 64 w, 4 sub-tiles of 16 keys.  Lane
 // l = 16g + i holds the cosines of query i with keys k0 + 16t + 4g + r (t, r in
 // 0..3) -- written as float4 rows of cw.
-template <int NCH>
+template <int NCH, bool MASK>
 __global__ void __launch_bounds__(256)
 clip_scores_kernel(int B, int N, int E, int offset, const float* __restrict__ img_all,
                    const float* __restrict__ txt_all, const float* __restrict__ logit_scale,
-                   float* __restrict__ ws) {
+                   float* __restrict__ ws, const int* __restrict__ cid_all) {
   const ClipWs L = clip_ws_layout(B, N, E);
   const int per_role = L.nqb * L.nkc;
   const int role = blockIdx.x / per_role;
@@ -110,12 +119,26 @@ clip_scores_kernel(int B, int N, int E, int offset, const float* __restrict__ im
   float* cw = ws + L.cw + ((size_t)role * L.Bp + q0 + x) * L.Np + k0;
 #pragma unroll
   for (int t = 0; t < 4; ++t) *reinterpret_cast<v4f*>(cw + 16 * t + 4 * g) = acc[t];
+  // MASK: bit 4t + r set = key k0 + 16t + 4g + r is a duplicate-caption negative of
+  // query q0 + x; dropped before the max, so it can neither set it nor enter the sum
+  unsigned drop = 0;
+  if constexpr (MASK) {
+    const int qglob = offset + q0 + x;
+    const int qid = q0 + x < B ? cid_all[qglob] : 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = k0 + 16 * t + 4 * g + r;
+        if (j < N && j != qglob && cid_all[j] == qid) drop |= 1u << (4 * t + r);
+      }
+  }
   float m = -INFINITY;
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (k0 + 16 * t + 4 * g + r < N) m = fmaxf(m, s * acc[t][r]);
+      if (k0 + 16 * t + 4 * g + r < N && !(drop >> (4 * t + r) & 1)) m = fmaxf(m, s * acc[t][r]);
   m = fmaxf(m, __shfl_xor(m, 16, 64));
   m = fmaxf(m, __shfl_xor(m, 32, 64));
   float sum = 0.f;
@@ -123,9 +146,11 @@ clip_scores_kernel(int B, int N, int E, int offset, const float* __restrict__ im
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (k0 + 16 * t + 4 * g + r < N) sum += expf(s * acc[t][r] - m);
+      if (k0 + 16 * t + 4 * g + r < N && !(drop >> (4 * t + r) & 1)) sum += expf(s * acc[t][r] - m);
   sum += __shfl_xor(sum, 16, 64);
   sum += __shfl_xor(sum, 32, 64);
+  // a tile with no kept key for this query (past N, or MASK: all dropped) never ran
+  // the expf above: it leaves (m, sum) = (-inf, 0), which launch 2's fold skips
   if (g == 0 && q0 + x < B) {
     const size_t o = ((size_t)role * L.Bp + q0 + x) * L.nkt + k0 / kKT;
     ws[L.pm + o] = m;
@@ -135,13 +160,16 @@ clip_scores_kernel(int B, int N, int E, int offset, const float* __restrict__ im
 
 // Launch 2.  Same grid as launch 1; wave w owns keys k0 = kc * 256 + 64 w in two
 // halves of 32 staged in LDS ([32][E + 4] per wave).  Lane l = 16g + i: query i.
-template <int NCH>
+// MASK: the caption ids sit behind the slabs -- [4][32] key ids (one slab's per
+// wave), the 16 query ids, and [16][16] partial counts of each query's dropped keys.
+template <int NCH, bool MASK>
 __global__ void __launch_bounds__(256)
 clip_dq_kernel(int B, int N, int E, int offset, const float* __restrict__ img_all,
                const float* __restrict__ txt_all, const float* __restrict__ logit_scale,
-               const float* __restrict__ role_w, float* __restrict__ ws) {
+               const float* __restrict__ role_w, float* __restrict__ ws, const int* __restrict__ cid_all) {
   constexpr int EP = NCH * 16 + 4;                       // LDS row stride (floats)
-  __shared__ __attribute__((aligned(16))) float lds[4 * 32 * EP];
+  constexpr int kIds = 4 * 32 + 16 + 16 * 16;
+  __shared__ __attribute__((aligned(16))) float lds[4 * 32 * EP + (MASK ? kIds : 0)];
   __shared__ float red_ds[4];
   const ClipWs L = clip_ws_layout(B, N, E);
   const int per_role = L.nqb * L.nkc;
@@ -181,6 +209,31 @@ clip_dq_kernel(int B, int N, int E, int offset, const float* __restrict__ img_al
   if (kc == 0 && w == 0 && g == 0 && qvalid) ws[L.lse + (size_t)role * L.Bp + q0 + x] = lse;
   const int qglob = offset + q0 + x;
   float* kl = lds + w * 32 * EP;
+  int* kid = nullptr;      // MASK: ids of this wave's staged keys
+  int qid = 0;             // MASK: id of query q0 + x
+  bool lone = false;       // MASK: every other key is dropped, the diagonal stands alone
+  if constexpr (MASK) {
+    int* ids = reinterpret_cast<int*>(lds + 4 * 32 * EP);
+    int* qs = ids + 4 * 32;
+    int* cs = qs + 16;
+    kid = ids + w * 32;
+    // thread (x, sixteenth c) counts the keys c, c + 16, .. that query q0 + x drops
+    const int c = threadIdx.x >> 4;
+    const int myid = qvalid ? cid_all[qglob] : 0;
+    int n = 0;
+    if (qvalid)
+      for (int j = c; j < N; j += 16) n += (j != qglob && cid_all[j] == myid) ? 1 : 0;
+    cs[c * 16 + x] = n;
+    if (c == 0) qs[x] = myid;
+    __syncthreads();
+    qid = qs[x];
+    int nd = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) nd += cs[i * 16 + x];
+    // exp(lg - lse) - 1 of a lone diagonal is only zero to rounding (lg and lse are the
+    // same product rounded apart): such a row is written as the exact zeros it is
+    lone = nd > 0 && nd == N - 1;
+  }
   float* cwrow = ws + L.cw + ((size_t)role * L.Bp + q0 + x) * L.Np;
   v4f acc[NCH];
 #pragma unroll
@@ -195,6 +248,8 @@ clip_dq_kernel(int B, int N, int E, int offset, const float* __restrict__ img_al
         const int row = e / (NCH * 4), c4 = e - row * (NCH * 4);
         *reinterpret_cast<v4f*>(kl + row * EP + 4 * c4) = ld_row4(ksrc, j0 + row, N, 4 * c4, E);
       }
+      if constexpr (MASK)
+        if (l < 32) kid[l] = j0 + l < N ? cid_all[j0 + l] : 0;
     }
     __syncthreads();
     if (active) {
@@ -210,9 +265,15 @@ clip_dq_kernel(int B, int N, int E, int offset, const float* __restrict__ img_al
           if (qvalid && jb + r < N) {
             const float lg = s * cv[r];
             const bool diag = jb + r == qglob;
-            wt = (expf(lg - lse) - (diag ? 1.f : 0.f)) * inv2n;
-            ds = fmaf(wt, cv[r], ds);
-            if (diag) ws[L.lterm + (size_t)role * L.Bp + q0 + x] = lse - lg;
+            bool keep = true;
+            if constexpr (MASK) keep = !lone && (diag || kid[16 * u + 4 * g + r] != qid);
+            if (keep) {
+              wt = (expf(lg - lse) - (diag ? 1.f : 0.f)) * inv2n;
+              ds = fmaf(wt, cv[r], ds);
+              if (diag) ws[L.lterm + (size_t)role * L.Bp + q0 + x] = lse - lg;
+            } else if (diag) {
+              ws[L.lterm + (size_t)role * L.Bp + q0 + x] = 0.f;
+            }
           }
           wr[r] = wt;
         }
@@ -382,18 +443,27 @@ __global__ void l2norm_bwd_kernel(int R, int E, const float* __restrict__ y, con
 
 // symmetric CE over an explicit [B][B] logits matrix (API path: _compute_loss)
 // out[0] = loss, out[1] = image loss, out[2] = text loss; dlogits = d loss / d logits
+// MASK: entries (i, j), i != j, with cid[i] == cid[j] are left out of both softmaxes
+// (vlp_clip_loss_fused_masked's rule on explicit logits); the diagonal keeps the max finite
+template <bool MASK>
 __global__ void ce_sym_kernel(int B, const float* __restrict__ logits, float* __restrict__ out,
-                              float* __restrict__ dlogits, const float* __restrict__ role_w) {
+                              float* __restrict__ dlogits, const float* __restrict__ role_w,
+                              const int* __restrict__ cid) {
   // role 0: rows, role 1: columns; one wave per row/column
   int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   int l = threadIdx.x & 63;
   if (w >= 2 * B) return;
   int role = w / B, i = w % B;
+  int ci = 0;
+  if constexpr (MASK) ci = cid[i];
+  auto kept = [&](int j) { return !MASK || j == i || cid[j] != ci; };
   float m = -INFINITY;
-  for (int j = l; j < B; j += 64) m = fmaxf(m, role ? logits[(size_t)j * B + i] : logits[(size_t)i * B + j]);
+  for (int j = l; j < B; j += 64)
+    if (kept(j)) m = fmaxf(m, role ? logits[(size_t)j * B + i] : logits[(size_t)i * B + j]);
   m = warp_max(m);
   float s = 0.f;
-  for (int j = l; j < B; j += 64) s += expf((role ? logits[(size_t)j * B + i] : logits[(size_t)i * B + j]) - m);
+  for (int j = l; j < B; j += 64)
+    if (kept(j)) s += expf((role ? logits[(size_t)j * B + i] : logits[(size_t)i * B + j]) - m);
   s = warp_sum(s);
   float lse = m + logf(s);
   float diag = logits[(size_t)i * B + i];
@@ -404,6 +474,7 @@ __global__ void ce_sym_kernel(int B, const float* __restrict__ logits, float* __
   if (dlogits) {   // d (sum_r role_w[r] * CE_r / 2) / d logits
     const float wr = (role_w ? role_w[role] : 1.f) * 0.5f / B;
     for (int j = l; j < B; j += 64) {
+      if (!kept(j)) continue;
       size_t o = role ? (size_t)j * B + i : (size_t)i * B + j;
       float p = expf(logits[o] - lse);
       atomicAdd(dlogits + o, wr * (p - (i == j ? 1.f : 0.f)));
@@ -443,11 +514,11 @@ VLP_EXPORT int vlp_clip_loss_ws_floats(int B, int N, int E, long long* n) {
   return 0;
 }
 
-VLP_EXPORT int vlp_clip_loss_fused(int B, int N, int E, int offset, const float* img_all,
-                                   const float* txt_all, const float* logit_scale, float* g_img_all,
-                                   float* g_txt_all, float* d_logit_scale, float* loss_parts,
-                                   float* lse_out, const float* role_w, float* ws, long long ws_floats,
-                                   void* stream) {
+template <bool MASK>
+static int clip_loss_run(int B, int N, int E, int offset, const float* img_all, const float* txt_all,
+                         const float* logit_scale, float* g_img_all, float* g_txt_all,
+                         float* d_logit_scale, float* loss_parts, float* lse_out, const float* role_w,
+                         const int* cid_all, float* ws, long long ws_floats, void* stream) {
   if (B < 1 || N < B || E < 4 || E > kMaxE || E % 4 || offset < 0 || offset + B > N)
     return (int)hipErrorInvalidValue;
   const ClipWs L = clip_ws_layout(B, N, E);
@@ -455,18 +526,39 @@ VLP_EXPORT int vlp_clip_loss_fused(int B, int N, int E, int offset, const float*
   hipStream_t st = (hipStream_t)stream;
   const dim3 g12(2 * L.nqb * L.nkc);
   if (E <= 128) {
-    hipLaunchKernelGGL(clip_scores_kernel<8>, g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale, ws);
-    hipLaunchKernelGGL(clip_dq_kernel<8>, g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale,
-                       role_w, ws);
+    hipLaunchKernelGGL((clip_scores_kernel<8, MASK>), g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale, ws,
+                       cid_all);
+    hipLaunchKernelGGL((clip_dq_kernel<8, MASK>), g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale,
+                       role_w, ws, cid_all);
   } else {
-    hipLaunchKernelGGL(clip_scores_kernel<16>, g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale, ws);
-    hipLaunchKernelGGL(clip_dq_kernel<16>, g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale,
-                       role_w, ws);
+    hipLaunchKernelGGL((clip_scores_kernel<16, MASK>), g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale, ws,
+                       cid_all);
+    hipLaunchKernelGGL((clip_dq_kernel<16, MASK>), g12, dim3(256), 0, st, B, N, E, offset, img_all, txt_all, logit_scale,
+                       role_w, ws, cid_all);
   }
   const int ncg = (E + 16 * kETW - 1) / (16 * kETW);
   hipLaunchKernelGGL(clip_dk_kernel, dim3(2 * (L.Np / kKB) * ncg), dim3(256), 0, st, B, N, E, offset, img_all,
                      txt_all, logit_scale, (const float*)ws, g_img_all, g_txt_all, d_logit_scale, loss_parts, lse_out);
   return (int)hipGetLastError();
+}
+
+VLP_EXPORT int vlp_clip_loss_fused(int B, int N, int E, int offset, const float* img_all,
+                                   const float* txt_all, const float* logit_scale, float* g_img_all,
+                                   float* g_txt_all, float* d_logit_scale, float* loss_parts,
+                                   float* lse_out, const float* role_w, float* ws, long long ws_floats,
+                                   void* stream) {
+  return clip_loss_run<false>(B, N, E, offset, img_all, txt_all, logit_scale, g_img_all, g_txt_all,
+                              d_logit_scale, loss_parts, lse_out, role_w, nullptr, ws, ws_floats, stream);
+}
+
+VLP_EXPORT int vlp_clip_loss_fused_masked(int B, int N, int E, int offset, const float* img_all,
+                                          const float* txt_all, const float* logit_scale, const int* cid_all,
+                                          float* g_img_all, float* g_txt_all, float* d_logit_scale,
+                                          float* loss_parts, float* lse_out, const float* role_w, float* ws,
+                                          long long ws_floats, void* stream) {
+  if (!cid_all) return (int)hipErrorInvalidValue;
+  return clip_loss_run<true>(B, N, E, offset, img_all, txt_all, logit_scale, g_img_all, g_txt_all,
+                             d_logit_scale, loss_parts, lse_out, role_w, cid_all, ws, ws_floats, stream);
 }
 
 VLP_EXPORT int vlp_l2norm_fwd(int R, int E, const float* x, float* y, float* norm, void* stream) {
@@ -503,8 +595,16 @@ VLP_EXPORT int vlp_clip_loss_finish(const float* parts, int N, float* out, void*
 
 VLP_EXPORT int vlp_ce_sym(int B, const float* logits, float* out, float* dlogits, const float* role_w,
                           void* stream) {
-  hipLaunchKernelGGL(ce_sym_kernel, dim3((2 * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, logits,
-                     out, dlogits, role_w);
+  hipLaunchKernelGGL(ce_sym_kernel<false>, dim3((2 * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, logits,
+                     out, dlogits, role_w, (const int*)nullptr);
+  return (int)hipGetLastError();
+}
+
+VLP_EXPORT int vlp_ce_sym_masked(int B, const float* logits, const int* cid, float* out, float* dlogits,
+                                 const float* role_w, void* stream) {
+  if (!cid) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(ce_sym_kernel<true>, dim3((2 * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, logits,
+                     out, dlogits, role_w, cid);
   return (int)hipGetLastError();
 }
 

@@ -11,6 +11,8 @@ Reference behaviour kept:
     3 channels (:165-171), "caption_tokenized" {input_ids, token_type_ids,
     attention_mask} [B,T] int64 padded to at most 40 tokens (:210-215), "label"
     [B], and the string lists "caption", "dataset", "anatomy_site", "image_path";
+    added: "caption_id" [B] int64, equal exactly where the captions are equal (the
+    key of VisionLanguageModule's duplicate_caption_mask);
   * get_cv_splits() yields (datamodule, label_weights) (:270), train_dataloader()
     with pin_memory=True, val_dataloader() -> [lera_val, mura_val] (:318-350).
 
@@ -22,7 +24,10 @@ MI355X-first changes:
   * DevicePrefetcher copies batch i+1 to HBM on a side HIP stream while step i
     runs and hands it over with a stream-ordered event wait, so the PCIe copy
     is off the step's critical path.
-  * image_size (default 224, the reference's) and the synthetic dataset.
+  * image_size (default 224, the reference's) and the synthetic dataset;
+    n_unique_captions draws the synthetic captions from a pool of that many, the
+    same pool on every rank (880 in the reference's caption file), so
+    that global batches repeat captions as real ones must.
 
   * the training augmentations run on the device (device_augment ->
     vlp_amd.augment, csrc/prep_ops.hip), called by the trainer on each training
@@ -62,10 +67,17 @@ class SyntheticRadiographCaptions(Dataset):
     """Seeded per-sample radiograph/caption dicts in the reference's sample layout."""
 
     def __init__(self, n: int, image_size: int, seq_len: int = MAX_TOKENS, seed: int = 0,
-                 dataset_name: str = "MURA"):
+                 dataset_name: str = "MURA", n_unique_captions: Optional[int] = None,
+                 caption_seed: Optional[int] = None):
+        """n_unique_captions (None: one caption per sample): sample i carries caption
+        i % n_unique_captions of a pool drawn with caption_seed (default: seed)."""
         if seq_len < 3 or seq_len > MAX_TOKENS:
             raise ValueError(f"seq_len must be in [3, {MAX_TOKENS}], got {seq_len}")
+        if n_unique_captions is not None and n_unique_captions < 1:
+            raise ValueError(f"n_unique_captions must be positive, got {n_unique_captions}")
         self.n, self.H, self.T, self.seed, self.name = n, image_size, seq_len, seed, dataset_name
+        self.n_unique = n_unique_captions
+        self.caption_seed = seed if caption_seed is None or n_unique_captions is None else caption_seed
 
     def __len__(self):
         return self.n
@@ -73,7 +85,18 @@ class SyntheticRadiographCaptions(Dataset):
     def __getitem__(self, i: int) -> dict:
         if not 0 <= i < self.n:
             raise IndexError(i)
-        g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
+        s = self._draw(self.seed, i)
+        c = i if self.n_unique is None else i % self.n_unique
+        if self.n_unique is not None:
+            # the caption fields of pool entry c (its own draw; image and label stay sample i's)
+            cap = self._draw(self.caption_seed, c)
+            for k in ("caption_tokenized", "caption", "anatomy_site"):
+                s[k] = cap[k]
+        s["caption_id"] = self.caption_seed * 1_000_003 + c
+        return s
+
+    def _draw(self, seed: int, i: int) -> dict:
+        g = torch.Generator().manual_seed(seed * 1_000_003 + i)
         img = torch.randint(0, 256, (1, self.H, self.H), generator=g, dtype=torch.uint8)
         L = min(int(torch.randint(8, 21, (1,), generator=g)), self.T - 2)
         ids = torch.full((self.T,), PAD_ID, dtype=torch.long)
@@ -121,6 +144,8 @@ class PairCollator:
         }
         for k in ("caption", "dataset", "anatomy_site", "image_path"):
             batch[k] = [s[k] for s in samples]
+        if "caption_id" in samples[0]:   # a tensor like the tokens: pinned with them by the loader
+            batch["caption_id"] = torch.tensor([s["caption_id"] for s in samples], dtype=torch.long)
         if self.upload == "u8":
             if self.num_channels != 3:
                 raise ValueError("the u8 upload feeds the 3-channel ImageNet-layout stem")
@@ -223,6 +248,7 @@ class PretrainDataModule:
         upload: str = "u8",
         seed: int = 0,
         drop_last: bool = True,
+        n_unique_captions: Optional[int] = None,
     ):
         if not (num_channels == 1 or num_channels == 3):
             raise ValueError(f"PretrainDataModule: num_channels must be 1 or 3, but got {num_channels}")
@@ -243,9 +269,11 @@ class PretrainDataModule:
         n = n_samples if try_with_only_n_samples is None else min(n_samples, try_with_only_n_samples)
         nv = n_val_samples if try_with_only_n_samples is None else min(n_val_samples, try_with_only_n_samples)
         rank = torch.distributed.get_rank() if torch.distributed.is_initialized() else 0
-        self.train_dataset = SyntheticRadiographCaptions(n, image_size, seq_len, seed + 7919 * rank, "MURA")
-        self.val_datasets = [SyntheticRadiographCaptions(nv, image_size, seq_len, seed + 1_000 + rank, "LERA"),
-                             SyntheticRadiographCaptions(nv, image_size, seq_len, seed + 2_000 + rank, "MURA")]
+        self.n_unique_captions = n_unique_captions
+        cap = dict(n_unique_captions=n_unique_captions, caption_seed=seed)   # one caption pool for all ranks
+        self.train_dataset = SyntheticRadiographCaptions(n, image_size, seq_len, seed + 7919 * rank, "MURA", **cap)
+        self.val_datasets = [SyntheticRadiographCaptions(nv, image_size, seq_len, seed + 1_000 + rank, "LERA", **cap),
+                             SyntheticRadiographCaptions(nv, image_size, seq_len, seed + 2_000 + rank, "MURA", **cap)]
         # per-fold intensity statistics of the training images (the reference computes and
         # caches them per fold, :217-267, for NormalizeIntensityd)
         self.image_mean, self.image_std = self._intensity_stats(self.train_dataset)

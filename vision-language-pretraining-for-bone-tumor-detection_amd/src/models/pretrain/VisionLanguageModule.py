@@ -16,6 +16,10 @@ Additions (keyword-only, defaults keep reference behaviour where possible):
   fused_optimizer  build vlp_amd.FusedAdamW when the configured optimizer is
                    torch.optim.AdamW (same hyper-parameters / param groups)
   device         where the parameter arenas live (default: cuda)
+  duplicate_caption_mask  (in **kwargs, default False) leave duplicate-caption negatives
+                 out of the contrastive loss: under data parallelism the global batch
+                 repeats captions, which the reference's per-process sampler cannot
+                 prevent (vlp_clip_loss_fused_masked)
 """
 from __future__ import annotations
 
@@ -36,7 +40,8 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from vlp_amd import ops  # noqa: E402
-from vlp_amd.clip_model import ClipHead, ClipStepFn, _project_normalize, role_weights  # noqa: E402
+from vlp_amd.clip_model import (ClipHead, ClipStepFn, _project_normalize, caption_hash64,  # noqa: E402
+                                compact_caption_ids, role_weights)
 from vlp_amd.optim import FusedAdamW  # noqa: E402
 from vlp_amd.nest import NEST_CFGS, NestTower  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
@@ -220,12 +225,17 @@ class _SymCEFn(torch.autograd.Function):
     All three outputs are differentiable, as the reference's autograd tensors are."""
 
     @staticmethod
-    def forward(ctx, logits):
+    def forward(ctx, logits, cid=None):
+        """cid (optional, int32 [B]): duplicate-caption negatives are left out (vlp_ce_sym_masked)."""
         lg = logits.float().contiguous()
         out = torch.zeros(3, dtype=torch.float32, device=lg.device)
         dl = torch.zeros_like(lg)
-        ops.ce_sym(lg, out, dl)
+        if cid is None:
+            ops.ce_sym(lg, out, dl)
+        else:
+            ops.ce_sym_masked(lg, cid, out, dl)
         ctx.save_for_backward(dl, lg)
+        ctx.cid = cid
         ctx.set_materialize_grads(False)
         return out[0], out[1], out[2]
 
@@ -234,15 +244,19 @@ class _SymCEFn(torch.autograd.Function):
         dl, lg = ctx.saved_tensors
         if gi is None and gt is None:
             if gl is None:
-                return None
+                return None, None
             out = torch.empty_like(dl)
             ops.scale(dl, gl.reshape(1).float().contiguous(), out)
-            return out
+            return out, None
         # gl*loss + gi*image_loss + gt*text_loss = sum_r (gl + 2 g_r) * CE_r / 2
         w = role_weights(gl, gi, gt, lg.device)
         out = torch.zeros_like(lg)
-        ops.ce_sym(lg, torch.zeros(3, dtype=torch.float32, device=lg.device), out, role_w=w)
-        return out
+        scratch = torch.zeros(3, dtype=torch.float32, device=lg.device)
+        if ctx.cid is None:
+            ops.ce_sym(lg, scratch, out, role_w=w)
+        else:
+            ops.ce_sym_masked(lg, ctx.cid, scratch, out, role_w=w)
+        return out, None
 
 
 def _logit_scale_fp64(module, state_dict, prefix, local_metadata):
@@ -295,6 +309,7 @@ class VisionLanguageModule(_Base):
                   image_encoder_lr=image_encoder_lr, projections_lr=projections_lr,
                   image_encoder_droupout=image_encoder_droupout, compute_dtype=compute_dtype,
                   text_dropout=text_dropout, fused_optimizer=fused_optimizer, **kwargs)
+        hp["duplicate_caption_mask"] = bool(kwargs.get("duplicate_caption_mask", False))
         if _HAVE_LIGHTNING:  # pragma: no cover
             self.save_hyperparameters(logger=False)
         else:
@@ -427,14 +442,31 @@ class VisionLanguageModule(_Base):
         logits = _LogitsFn.apply(ie, te, self.logit_scale)
         return logits, ie, te
 
-    def _compute_loss(self, logits, deduplicate: bool = True, masked: bool = False, captions=None):
+    def _caption_keys(self, batch):
+        """One integer key per caption of the batch, equal for equal captions on every
+        rank: the datamodule's "caption_id" tensor when it carries one, else a 64-bit
+        hash of the "caption" strings (None with duplicate_caption_mask off)."""
+        if not self.hparams.get("duplicate_caption_mask", False):
+            return None
+        cid = batch.get("caption_id")
+        if cid is None:
+            cid = caption_hash64(batch["caption"])
+        return cid.to(self.device, non_blocking=True)
+
+    def _compute_loss(self, logits, deduplicate: bool = True, masked: bool = False, captions=None,
+                      caption_ids=None):
+        """caption_ids (integer keys [B], used with duplicate_caption_mask only): entries
+        (i, j), i != j, of equal captions are left out of both softmaxes -- not the retired
+        `logits * mask` (:506-530), whose masked logits stay in the denominator as exp(0)."""
         if deduplicate:                                                              # :535-545
             raise DeprecationWarning(
                 "Deduplication loss was made obsolete by generating diverse captions and the custom batch sampler")
         if masked:
             raise DeprecationWarning(
                 "Masked loss was made obsolete by generating diverse captions and the custom batch sampler")
-        return _SymCEFn.apply(logits)
+        if caption_ids is not None and self.hparams.get("duplicate_caption_mask", False):
+            return _SymCEFn.apply(logits, compact_caption_ids(caption_ids.to(logits.device).to(torch.int64)))
+        return _SymCEFn.apply(logits, None)
 
     def training_step_outputs(self, batch):
         """Fused hot path: loss, image_loss, text_loss, img_emb, txt_emb (global batch under DP)."""
@@ -456,6 +488,7 @@ class VisionLanguageModule(_Base):
             raise DeprecationWarning("deduplicate / masked loss were removed by the reference (:535-545)")
         towers = self._towers()
         towers.u8_norm = tuple(batch.get("x-ray-u8-norm", (127.5, 73.9)))   # the collator's normalisation
+        towers.caption_ids = self._caption_keys(batch)   # None: the unmasked loss
         return ClipStepFn.apply(towers, x, x_u8, ids, am, tt, *self._all_params())
 
     def training_step(self, batch, batch_idx=None):
@@ -565,7 +598,7 @@ class VisionLanguageModule(_Base):
         logits, ie, te = self(batch)
         self._cache_embeddings_and_labels(ie, te, batch["label"], mode="val")
         loss, _, _ = self._compute_loss(logits, self.hparams["deduplicate"], self.hparams["masked_loss"],
-                                        batch.get("caption"))
+                                        batch.get("caption"), self._caption_keys(batch))
         if dataloader_idx == 0:
             log_path_str = "val/lera"
         elif dataloader_idx == 1:

@@ -138,8 +138,73 @@ def role_weights(gl, gi, gt, device):
     return torch.stack([wi, wt]).contiguous()
 
 
+def caption_hash64(captions) -> torch.Tensor:
+    """int64 [B] (host): a 64-bit hash of each caption string, the same on every rank
+    and in every run (BLAKE2b-64 of the UTF-8 bytes; Python's hash() is salted per
+    process).  The string is the caption's identity, as in the reference's
+    np.unique(captions) (VisionLanguageModule.py:506-530)."""
+    import hashlib
+    return torch.tensor([int.from_bytes(hashlib.blake2b(c.encode("utf-8"), digest_size=8).digest(),
+                                        "little", signed=True) for c in captions], dtype=torch.int64)
+
+
+def gather_caption_ids(cid: torch.Tensor) -> torch.Tensor:
+    """This rank's caption keys [B] (int64 hashes or a datamodule's caption_id) ->
+    int32 [N] ids of the gathered batch, in rank order with the embeddings' offsets:
+    equal keys get equal ids.  The keys are all-gathered (host-staged under gloo,
+    RCCL otherwise) and ranked on the device without a host synchronisation (sort,
+    run starts, prefix sum); they carry no gradient, so nothing returns."""
+    return compact_caption_ids(vdist.all_gather_rows(cid.detach().to(torch.int64).contiguous()))
+
+
+def compact_caption_ids(keys: torch.Tensor) -> torch.Tensor:
+    """int64 keys [n] -> int32 ids [n] in 0 .. n_unique - 1, equal keys to equal ids."""
+    srt, order = keys.sort()
+    new = torch.ones_like(srt)
+    new[0] = 0
+    new[1:] = (srt[1:] != srt[:-1]).to(srt.dtype)
+    ids = torch.empty_like(srt)
+    ids[order] = new.cumsum(0)
+    return ids.to(torch.int32).contiguous()
+
+
+def _loss_launch(B, N, E, off, ie_all, te_all, ls, cid_all, g_img_all, g_txt_all, d_ls, parts, role_w=None):
+    """vlp_clip_loss_fused, or its masked sibling when caption ids are given."""
+    if cid_all is None:
+        ops.clip_loss_fused(B, N, E, off, ie_all, te_all, ls, g_img_all, g_txt_all, d_ls, parts, role_w=role_w)
+    else:
+        ops.clip_loss_fused_masked(B, N, E, off, ie_all, te_all, ls, cid_all, g_img_all, g_txt_all, d_ls,
+                                   parts, role_w=role_w)
+
+
+def global_batch_loss(ie, te, ls, cid=None):
+    """The head's exchange and loss for this rank's normalised embeddings ie / te [B, E]:
+    all-gather (embeddings and, if given, the caption keys `cid`), the fused loss over
+    the rank's rows / columns of the global N x N matrix, all-reduce of the loss terms.
+    Returns out = {loss, image_loss, text_loss}, the gathered-embedding gradients
+    g_img_all / g_txt_all (the owners' rows come back by vdist.reduce_scatter_rows),
+    small = {parts[2], d_logit_scale, -}, and (ie_all, te_all, N, rank, cid_all)."""
+    B, E = ie.shape
+    rank, world = vdist.world()
+    ie_all = vdist.all_gather_rows(ie)
+    te_all = vdist.all_gather_rows(te)
+    cid_all = gather_caption_ids(cid.to(ie.device)) if cid is not None else None
+    N = B * world
+    dev = ie.device
+    g_img_all = torch.zeros(N, E, dtype=torch.float32, device=dev)
+    g_txt_all = torch.zeros(N, E, dtype=torch.float32, device=dev)
+    small = torch.zeros(4, dtype=torch.float32, device=dev)   # parts[2], d_logit_scale
+    _loss_launch(B, N, E, rank * B, ie_all, te_all, ls, cid_all, g_img_all, g_txt_all, small[2:3], small[0:2])
+    vdist.all_reduce_sum_(small[0:2])  # global loss terms (the gradient needs no collective)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    ops.clip_loss_finish(small[0:2], N, out)
+    return out, g_img_all, g_txt_all, small, (ie_all, te_all, N, rank, cid_all)
+
+
 class ClipStepFn(torch.autograd.Function):
-    """loss, image_loss, text_loss, img_emb, txt_emb = f(batch; all parameters)."""
+    """loss, image_loss, text_loss, img_emb, txt_emb = f(batch; all parameters).
+    `model.caption_ids` (optional, [B] integer keys): duplicate-caption negatives of
+    the global batch are masked out of the loss (vlp_clip_loss_fused_masked)."""
 
     @staticmethod
     def forward(ctx, model, x, x_u8, input_ids, attention_mask, token_type_ids, *params):
@@ -166,23 +231,11 @@ class ClipStepFn(torch.autograd.Function):
         Di = head.image_dim
         ie, inorm = _project_normalize(head, wT, feat_img, Di, Di, "image_projection", E)
         te, tnorm = _project_normalize(head, wT, h_last, D, D, "text_projection", E)
-        rank, world = vdist.world()
-        ie_all = vdist.all_gather_rows(ie)
-        te_all = vdist.all_gather_rows(te)
-        N = B * world
-        dev = ie.device
-        g_img_all = torch.zeros(N, E, dtype=torch.float32, device=dev)
-        g_txt_all = torch.zeros(N, E, dtype=torch.float32, device=dev)
-        small = torch.zeros(4, dtype=torch.float32, device=dev)   # parts[2], d_logit_scale
-        ls = head.arena.view("logit_scale")
-        ops.clip_loss_fused(B, N, E, rank * B, ie_all, te_all, ls, g_img_all, g_txt_all, small[2:3],
-                            small[0:2])
-        vdist.all_reduce_sum_(small[0:2])  # global loss terms (the gradient needs no collective)
-        out = torch.empty(3, dtype=torch.float32, device=dev)
-        ops.clip_loss_finish(small[0:2], N, out)
+        out, g_img_all, g_txt_all, small, gathered = global_batch_loss(
+            ie, te, head.arena.view("logit_scale"), getattr(model, "caption_ids", None))
         ctx.model = model
         ctx.state = (sv_img, sv_txt, wT, feat_img, h_last, ie, inorm, te, tnorm, g_img_all, g_txt_all,
-                     small, B, Tn, D, E, (ie_all, te_all, N, rank))
+                     small, B, Tn, D, E, gathered)
         ctx.mark_non_differentiable(ie, te)
         ctx.set_materialize_grads(False)   # an unused image_loss / text_loss costs nothing
         return out[0], out[1], out[2], ie, te
@@ -192,7 +245,7 @@ class ClipStepFn(torch.autograd.Function):
         model = ctx.model
         img_t, txt_t, head = model.image_tower, model.text_tower, model.head
         (sv_img, sv_txt, wT, feat_img, h_last, ie, inorm, te, tnorm, g_img_all, g_txt_all, small,
-         B, Tn, D, E, (ie_all, te_all, N, rank)) = ctx.state
+         B, Tn, D, E, (ie_all, te_all, N, rank, cid_all)) = ctx.state
         ctx.state = None
         for t in (head, img_t, txt_t):
             t.begin_backward()
@@ -206,8 +259,8 @@ class ClipStepFn(torch.autograd.Function):
             # autograd tensors): rerun the head with per-direction weights
             w = role_weights(dloss, dli, dlt, ie.device)
             scratch = torch.zeros(2, dtype=torch.float32, device=ie.device)
-            ops.clip_loss_fused(B, N, E, rank * B, ie_all, te_all, head.arena.view("logit_scale"), g_img_all,
-                                g_txt_all, small[2:3], scratch, role_w=w)
+            _loss_launch(B, N, E, rank * B, ie_all, te_all, head.arena.view("logit_scale"), cid_all, g_img_all,
+                         g_txt_all, small[2:3], scratch, role_w=w)
             gs = torch.ones(1, dtype=torch.float32, device=ie.device)
         g_img = vdist.reduce_scatter_rows(g_img_all)
         g_txt = vdist.reduce_scatter_rows(g_txt_all)

@@ -56,6 +56,9 @@ class _Done:
 
 
 def all_gather_rows(x: torch.Tensor) -> torch.Tensor:
+    """Rows of every rank in rank order (rank r's rows at offset r * rows).  Any dtype:
+    the fp32 embeddings and, with the duplicate-caption mask, the int64 caption keys
+    (clip_model.gather_caption_ids) take the same two paths, host-staged or RCCL."""
     r, w = world()
     if not active():
         return x

@@ -556,8 +556,33 @@ def clip_loss_fused(B, N, E, offset, img_all, txt_all, logit_scale, g_img_all, g
                               ptr(lse_out), ptr(role_w), ptr(ws), ws.numel(), _s())
 
 
+def _check_cid(cid, n):
+    if cid.dtype != torch.int32 or cid.numel() != n or not cid.is_contiguous():
+        raise TypeError(f"caption ids must be a contiguous int32 tensor of {n} elements, got "
+                        f"{cid.dtype} {tuple(cid.shape)}")
+
+
+def clip_loss_fused_masked(B, N, E, offset, img_all, txt_all, logit_scale, cid_all, g_img_all, g_txt_all,
+                           d_ls, loss_parts, lse_out=None, role_w=None):
+    """clip_loss_fused without the duplicate-caption negatives: cid_all int32 [N], entries
+    (i, j), i != j, with equal ids are left out of both softmaxes (same workspace)."""
+    import ctypes
+    _check_cid(cid_all, N)
+    n = ctypes.c_longlong(0)
+    lib().vlp_clip_loss_ws_floats(B, N, E, ctypes.addressof(n))
+    ws = _stream_ws("clip", img_all.device, n.value)
+    lib().vlp_clip_loss_fused_masked(B, N, E, offset, ptr(img_all), ptr(txt_all), ptr(logit_scale),
+                                     ptr(cid_all), ptr(g_img_all), ptr(g_txt_all), ptr(d_ls),
+                                     ptr(loss_parts), ptr(lse_out), ptr(role_w), ptr(ws), ws.numel(), _s())
+
+
 def ce_sym(logits, out, dlogits=None, role_w=None):
     lib().vlp_ce_sym(logits.shape[0], ptr(logits), ptr(out), ptr(dlogits), ptr(role_w), _s())
+
+
+def ce_sym_masked(logits, cid, out, dlogits=None, role_w=None):
+    _check_cid(cid, logits.shape[0])
+    lib().vlp_ce_sym_masked(logits.shape[0], ptr(logits), ptr(cid), ptr(out), ptr(dlogits), ptr(role_w), _s())
 
 
 def matmul(A, B, C, M, N, K, lda, a_kc, ldb, b_kc, ldc, alpha=1.0, accumulate=False, dtype_ref=None):
