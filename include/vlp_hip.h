@@ -257,13 +257,21 @@ int vlp_bn_grad_rep(int rep, int C, double* sum_g, double* sum_gx, double* sum_g
 int vlp_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
                        const float* running_var, float eps, float* scale, float* shift,
                        void* stream);
+/* Shapes of the streaming passes (vlp_bn_add_relu, vlp_bn_bwd_reduce, vlp_bn_bwd_apply,
+ * vlp_maxpool_bwd, vlp_maxpool_bwd_apply): a thread keeps one 16-byte channel chunk
+ * (8 bf16 / 4 fp32 elements), so C must be a multiple of the chunk, at least one chunk,
+ * with a chunk count C / chunk that divides 256 (bf16 C <= 2048, fp32 C <= 1024), and
+ * M (N, H, W) >= 1; anything else is hipErrorInvalidValue before any launch. */
 /* out = relu(sc*y + sh + idt'), idt' = idt (scd == NULL) or scd*idt + shd; idt == NULL: relu(sc*y + sh).
- * relu_mask (optional, bf16 only): out's sign bits, byte e>>3 bit e&7 = (out[e] > 0) */
+ * relu_mask (optional, bf16 only, else hipErrorInvalidValue): out's sign bits,
+ * byte e>>3 bit e&7 = (out[e] > 0) */
 int vlp_bn_add_relu(int dtype, long long M, int C, const void* y, const float* sc, const float* sh,
                     const void* idt, const float* scd, const float* shd, void* out, uint8_t* relu_mask,
                     void* stream);
 /* g = dout * (mask > 0) (dout may be a broadcast [N][C]/HW gradient `dbc`);
- * sum_g += sum g, sum_ga += sum g*xhat(ya), sum_gb += sum g*xhat(yb) */
+ * sum_g += sum g, sum_ga += sum g*xhat(ya), sum_gb += sum g*xhat(yb) (yb optional).
+ * mask, ya, mean_a, istd_a and one of dout / dbc are required, HW >= 1 with dbc:
+ * hipErrorInvalidValue otherwise. */
 int vlp_bn_bwd_reduce(int dtype, long long M, int C, const void* dout, const float* dbc, int HW,
                       const void* mask, const void* ya, const float* mean_a, const float* istd_a,
                       const void* yb, const float* mean_b, const float* istd_b, double* sum_g,
@@ -272,7 +280,9 @@ int vlp_bn_bwd_reduce(int dtype, long long M, int C, const void* dout, const flo
  * sums already folded, as vlp_bn_bwd_apply reads them) */
 int vlp_bn_bwd_coef(long long M, int C, const float* gamma, const float* istd, const float* mean,
                     const double* sum_g, const double* sum_gx, float* coef, void* stream);
-/* dy_s = gamma_s*istd_s*(g - mean(g) - xhat_s*mean(g*xhat_s)) for sides a, b; g_out = g. */
+/* dy_s = gamma_s*istd_s*(g - mean(g) - xhat_s*mean(g*xhat_s)) for sides a, b; g_out = g.
+ * Side a (ya, dy_a) and one of dout / dbc are required (HW >= 1 with dbc); side b is
+ * selected by dy_b and then needs yb: hipErrorInvalidValue otherwise. */
 int vlp_bn_bwd_apply(int dtype, long long M, int C, const void* dout, const float* dbc, int HW,
                      const void* mask, const void* ya, const float* mean_a, const float* istd_a,
                      const float* gamma_a, const double* sum_g_a, const double* sum_gx_a,

@@ -992,6 +992,14 @@ static inline int ew_variant() {
 static inline int ewb_variant() {
   return 0;
 }
+// Every streaming pass gives a thread ONE channel chunk (c0 = thread % cpr): the
+// rows must be whole 16-byte chunks (C a multiple of epc, at least one) and the
+// chunk count per row must divide the 256 threads of a workgroup.  Checked
+// before any division by cpr = C / epc.
+static inline bool ew_shape_ok(int dtype, long long M, int C) {
+  const int epc = dtype == VLP_BF16 ? 8 : 4;
+  return M >= 1 && C >= epc && C % epc == 0 && 256 % (C / epc) == 0;
+}
 
 }  // namespace vlp
 
@@ -1047,9 +1055,9 @@ VLP_EXPORT int vlp_bn_add_relu(int dtype, long long M, int C, const void* y, con
   hipStream_t st = (hipStream_t)stream;
   int epc = dtype == VLP_BF16 ? 8 : 4;
   if (relu_mask && dtype != VLP_BF16) return (int)hipErrorInvalidValue;
+  if (!ew_shape_ok(dtype, M, C)) return (int)hipErrorInvalidValue;
   unsigned n = (unsigned)((size_t)M * C / epc);
   int cpr = C / epc;
-  if (256 % cpr) return (int)hipErrorInvalidValue;
   dim3 g(ew_grid(n));
   const int form = dtype == VLP_BF16 ? ew_form_add_relu((size_t)n * 16, idt != nullptr) : 0;
   if (form > 0) {
@@ -1096,6 +1104,8 @@ VLP_EXPORT int vlp_bn_bwd_reduce(int dtype, long long M, int C, const void* dout
                                  const float* istd_b, double* sum_g, double* sum_ga, double* sum_gb,
                                  int stat_rep, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (!ew_shape_ok(dtype, M, C)) return (int)hipErrorInvalidValue;
+  if (!mask || !ya || !mean_a || !istd_a || (!dout && !dbc) || (dbc && HW < 1)) return (int)hipErrorInvalidValue;
   int epc = dtype == VLP_BF16 ? 8 : 4;
   int rows_per_iter = 256 / (C / epc);
   int blocks = ew_blocks((size_t)M, rows_per_iter * 16, 2048);
@@ -1122,9 +1132,10 @@ VLP_EXPORT int vlp_bn_bwd_apply(int dtype, long long M, int C, const void* dout,
   hipStream_t st = (hipStream_t)stream;
   BnBwdSide A{ya, mean_a, istd_a, gamma_a, sum_g_a, sum_gx_a, dy_a};
   BnBwdSide B{yb, mean_b, istd_b, gamma_b, sum_g_b, sum_gx_b, dy_b};
+  if (!ew_shape_ok(dtype, M, C)) return (int)hipErrorInvalidValue;
+  if (!ya || !dy_a || (dy_b && !yb) || (!dout && !dbc) || (dbc && HW < 1)) return (int)hipErrorInvalidValue;
   int epc = dtype == VLP_BF16 ? 8 : 4;
   int cpr = C / epc;
-  if (256 % cpr) return (int)hipErrorInvalidValue;
   unsigned n = (unsigned)((size_t)M * C / epc);
   dim3 g(ew_grid(n));
   bool hb = dy_b != nullptr;
@@ -1221,8 +1232,7 @@ VLP_EXPORT int vlp_maxpool_bwd(int dtype, int N, int H, int W, int C, const void
                                double* sum_gx, int stat_rep, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  int epc = dtype == VLP_BF16 ? 8 : 4;
-  if (256 % (C / epc)) return (int)hipErrorInvalidValue;
+  if (N < 1 || H < 1 || W < 1 || !ew_shape_ok(dtype, 1, C)) return (int)hipErrorInvalidValue;
   if (stat_rep < 1) stat_rep = 1;
   if (!(H & 1) && !(W & 1)) {
     dim3 g2((unsigned)(N * ((H / 2 + kMpPairs - 1) / kMpPairs)));
@@ -1255,8 +1265,7 @@ VLP_EXPORT int vlp_maxpool_bwd_apply(int dtype, int N, int H, int W, int C, cons
                                      void* dy, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  int epc = dtype == VLP_BF16 ? 8 : 4;
-  if (256 % (C / epc)) return (int)hipErrorInvalidValue;
+  if (N < 1 || H < 1 || W < 1 || !ew_shape_ok(dtype, 1, C)) return (int)hipErrorInvalidValue;
   if (!(H & 1) && !(W & 1)) {
     dim3 g2((unsigned)(N * ((H / 2 + kMpPairs - 1) / kMpPairs)));
     if (dtype == VLP_BF16)
