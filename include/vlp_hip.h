@@ -345,7 +345,11 @@ int vlp_linear_wgrad_ws_floats(int M, int Nout, int Kin, long long* n);
 /* out[n] += sum_m x[m][n] (bias gradients; fp32 atomics) */
 int vlp_colsum(int dtype, int M, int N, const void* x, int ld, float* out, void* stream);
 /* LayerNorm over rows of D <= 1024 (D a multiple of 8 for bf16, 4 for fp32), else
- * hipErrorInvalidValue */
+ * hipErrorInvalidValue.  A dropout probability (p, p_out, p_in) outside [0, 1) is refused with
+ * hipErrorInvalidValue (1 / (1 - p) would be infinite), M < 1 is a no-op that returns 0, and with
+ * M >= 1 a NULL x, gamma, beta, y, mean, rstd (forward) or dy, x, mean, rstd, gamma, dx, dgamma,
+ * dbeta (backward) is refused with hipErrorInvalidValue; dxd and addend may be NULL.  Nothing is
+ * launched by a refused call. */
 int vlp_layernorm_fwd(int dtype, int M, int D, const void* x, const float* gamma,
                       const float* beta, float eps, void* y, float* mean, float* rstd, float p,
                       unsigned long long seed, void* stream);
@@ -363,18 +367,25 @@ int vlp_layernorm_bwd_add_rs(int dtype, int M, int D, const void* dy, const void
                              const float* rstd, const float* gamma, const void* addend, void* dx, void* dxs,
                              const float* rscale, int rps, float* dgamma, float* dbeta, void* stream);
 /* softmax attention of one (sequence, head) per workgroup: T <= 64, 1 <= dh <= 64 (head
- * channels padded to 32 or 64 in LDS), else hipErrorInvalidValue */
+ * channels padded to 32 or 64 in LDS), else hipErrorInvalidValue.  Also refused with
+ * hipErrorInvalidValue, before any launch: a dropout probability p outside [0, 1), a NULL qkv,
+ * ctx or P (forward), a NULL qkv, P, dctx or dqkv (backward).  amask may be NULL (no key masked). */
 int vlp_attn_fwd(int dtype, int B, int T, int H, int dh, const void* qkv, const long long* amask,
                  void* ctx, float* P, float scale, float p, unsigned long long seed, void* stream);
 int vlp_attn_bwd(int dtype, int B, int T, int H, int dh, const void* qkv, const float* P,
                  const void* dctx, void* dqkv, float scale, float p, unsigned long long seed,
                  void* stream);
-/* temb / dtemb NULL: a model without a token-type table (DistilBERT) */
+/* temb / dtemb NULL: a model without a token-type table (DistilBERT); tt given without a table
+ * is ignored.  Refused with hipErrorInvalidValue before any division or launch: M < 1, T < 1,
+ * D < 1, M % T != 0, a NULL ids, wemb, pemb or e_out (forward), a NULL ids, de, dwemb or dpemb
+ * (backward). */
 int vlp_embed_fwd(int dtype, int M, int T, int D, const long long* ids, const long long* tt,
                   const float* wemb, const float* pemb, const float* temb, void* e_out,
                   void* stream);
 int vlp_embed_bwd(int dtype, int M, int T, int D, const long long* ids, const long long* tt,
                   const void* de, float* dwemb, float* dpemb, float* dtemb, void* stream);
+/* out[r * ldo + c] = in[r * ldi + c], r < R, c < D.  R < 1, D < 1, ldi < D, ldo < D or a NULL
+ * pointer: hipErrorInvalidValue, nothing launched. */
 int vlp_scatter_rows(int dtype, int R, int D, const void* in, int ldi, void* out, int ldo,
                      void* stream);
 
@@ -392,7 +403,9 @@ int vlp_row_topk(int R, int N, const float* x, long long ldx, int K, float* vals
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,
  * head h at h*32), out[BT*N][C] head-major (h*32 + d; timm's d*H + h order is folded into
  * the proj weight with vlp_nest_permute_cols), lse[BT*H*N] (log2 domain), head dim 32.
- * Backward: delta[BT*H*N] scratch; writes every column of dqkv. */
+ * Backward: delta[BT*H*N] scratch; writes every column of dqkv.  A NULL qkv, out, lse (forward)
+ * or qkv, out, dout, lse, delta, dqkv (backward) is refused with hipErrorInvalidValue before any
+ * launch, here and in vlp_vit_attn_*. */
 int vlp_nest_attn_fwd(int dtype, int BT, int H, int N, int dh, const void* qkv, void* out, float* lse,
                       float scale, void* stream);
 int vlp_nest_attn_bwd(int dtype, int BT, int H, int N, int dh, const void* qkv, const void* out,

@@ -1067,6 +1067,8 @@ static void ln_fwd_t(int M, int D, const void* x, const float* gamma, const floa
 }
 // chunks per lane: ceil(D / (16 elements-per-chunk... x 16 lanes))
 constexpr int kMaxLnD = 1024;
+// a dropout probability the kernels can honour: 1 / (1 - p) is finite on [0, 1) only (NaN fails both tests)
+static bool drop_p_ok(float p) { return p >= 0.f && p < 1.f; }
 static int ln_nch(int dtype, int D) {
   const int e = dtype == VLP_BF16 ? 8 : 4;
   if (D < 1 || D > kMaxLnD || D % e) return -1;
@@ -1101,8 +1103,9 @@ VLP_EXPORT int vlp_layernorm_fwd(int dtype, int M, int D, const void* x, const f
                                  const float* beta, float eps, void* y, float* mean, float* rstd,
                                  float p, unsigned long long seed, void* stream) {
   const int nch = ln_nch(dtype, D);
-  if (nch < 0) return (int)hipErrorInvalidValue;
+  if (nch < 0 || !drop_p_ok(p)) return (int)hipErrorInvalidValue;
   if (M < 1) return 0;
+  if (!x || !gamma || !beta || !y || !mean || !rstd) return (int)hipErrorInvalidValue;
   LN_DISPATCH(ln_fwd_t, dtype, nch, M, D, x, gamma, beta, eps, y, mean, rstd, p, seed, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
@@ -1151,8 +1154,9 @@ static int layernorm_bwd_launch(int dtype, int M, int D, const void* dy, float p
                                 float p_in, unsigned long long seed_in, float* dgamma, float* dbeta,
                                 const void* addend, const float* rscale, int rps, void* stream) {
   const int nch = ln_nch(dtype, D);
-  if (nch < 0 || (rscale && rps < 1)) return (int)hipErrorInvalidValue;
+  if (nch < 0 || (rscale && rps < 1) || !drop_p_ok(p_out) || !drop_p_ok(p_in)) return (int)hipErrorInvalidValue;
   if (M < 1) return 0;
+  if (!dy || !x || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta) return (int)hipErrorInvalidValue;
   LN_DISPATCH(ln_bwd_t, dtype, nch, M, D, dy, p_out, seed_out, x, mean, rstd, gamma, dx, dxd, p_in, seed_in, dgamma,
               dbeta, addend, rscale, rps, (hipStream_t)stream);
   return (int)hipGetLastError();
@@ -1227,6 +1231,7 @@ VLP_EXPORT int vlp_attn_fwd(int dtype, int B, int Tn, int H, int dh, const void*
                             const long long* amask, void* ctx, float* P, float scale, float p,
                             unsigned long long seed, void* stream) {
   if (Tn < 1 || Tn > kMaxT || dh < 1 || dh > kMaxDh || B < 1 || H < 1) return (int)hipErrorInvalidValue;
+  if (!drop_p_ok(p) || !qkv || !ctx || !P) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const bool small = Tn <= 48, wide = dh > 32;
   return ATTN_DISPATCH(launch_attn_fwd, dtype, small, wide, B, Tn, H, dh, qkv, amask, ctx, P, scale, p, seed, st);
@@ -1236,6 +1241,7 @@ VLP_EXPORT int vlp_attn_bwd(int dtype, int B, int Tn, int H, int dh, const void*
                             const void* dctx, void* dqkv, float scale, float p,
                             unsigned long long seed, void* stream) {
   if (Tn < 1 || Tn > kMaxT || dh < 1 || dh > kMaxDh || B < 1 || H < 1) return (int)hipErrorInvalidValue;
+  if (!drop_p_ok(p) || !qkv || !P || !dctx || !dqkv) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const bool small = Tn <= 48, wide = dh > 32;
   return ATTN_DISPATCH(launch_attn_bwd, dtype, small, wide, B, Tn, H, dh, qkv, P, dctx, dqkv, scale, p, seed, st);
@@ -1245,6 +1251,8 @@ VLP_EXPORT int vlp_embed_fwd(int dtype, int M, int Tn, int D, const long long* i
                              const long long* tt, const float* wemb, const float* pemb,
                              const float* temb, void* e_out, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  // (tt without a table is ignored: the kernel reads tt[] but adds no token-type term)
+  if (M < 1 || Tn < 1 || D < 1 || M % Tn || !ids || !wemb || !pemb || !e_out) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16)
     hipLaunchKernelGGL(embed_fwd_kernel<bf16>, dim3(M), dim3(128), 0, st, M, Tn, D,
                        (const int64_t*)ids, (const int64_t*)tt, wemb, pemb, temb, (bf16*)e_out);
@@ -1258,7 +1266,8 @@ VLP_EXPORT int vlp_embed_bwd(int dtype, int M, int Tn, int D, const long long* i
                              const long long* tt, const void* de, float* dwemb, float* dpemb,
                              float* dtemb, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (M % Tn) return (int)hipErrorInvalidValue;
+  // before the division by Tn and any launch
+  if (M < 1 || Tn < 1 || D < 1 || M % Tn || !ids || !de || !dwemb || !dpemb) return (int)hipErrorInvalidValue;
   const dim3 gpt(Tn, (D + 63) / 64);
   if (dtype == VLP_BF16) {
     hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3(M), dim3(128), 0, st, M, Tn, D,
@@ -1277,6 +1286,7 @@ VLP_EXPORT int vlp_embed_bwd(int dtype, int M, int Tn, int D, const long long* i
 VLP_EXPORT int vlp_scatter_rows(int dtype, int R, int D, const void* in, int ldi, void* out, int ldo,
                                 void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  if (R < 1 || D < 1 || ldi < D || ldo < D || !in || !out) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16)
     hipLaunchKernelGGL(scatter_rows_kernel<bf16>, dim3(R), dim3(128), 0, st, R, D, (const bf16*)in,
                        ldi, (bf16*)out, ldo);

@@ -904,6 +904,7 @@ template <int DH>
 static int attn_fwd_dh(int dtype, int BT, int H, int N, const void* qkv, void* out, float* lse, float scale,
                        void* stream) {
   if (BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (!qkv || !out || !lse) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) attn_fwd_t<bf16, DH>(BT, H, N, qkv, out, lse, scale, (hipStream_t)stream);
   else attn_fwd_t<float, DH>(BT, H, N, qkv, out, lse, scale, (hipStream_t)stream);
   return (int)hipGetLastError();
@@ -937,6 +938,7 @@ template <int DH>
 static int attn_bwd_dh(int dtype, int BT, int H, int N, const void* qkv, const void* out, const void* dout,
                        const float* lse, float* delta, void* dqkv, float scale, void* stream) {
   if (BT < 1 || H < 1 || N < 1 || (long long)((N + 63) / 64) * H * BT >= (1ll << 31)) return (int)hipErrorInvalidValue;
+  if (!qkv || !out || !dout || !lse || !delta || !dqkv) return (int)hipErrorInvalidValue;
   if (dtype == VLP_BF16) attn_bwd_t<bf16, DH>(BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, (hipStream_t)stream);
   else attn_bwd_t<float, DH>(BT, H, N, qkv, out, dout, lse, delta, dqkv, scale, (hipStream_t)stream);
   return (int)hipGetLastError();
