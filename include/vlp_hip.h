@@ -526,6 +526,31 @@ int vlp_cast(int dtype, long long n, const float* x, void* y, void* stream);
  * (VisionLanguageModule.py:130-184, configs/optimizer/adamw.yaml:1-3). */
 int vlp_adamw(long long n, float* p, const float* g, float* m, float* v, float lr, float beta1,
               float beta2, float eps, float wd, float step_size, float bc2_sqrt, void* stream);
+/* Gradient clipping on the device: replace torch.nn.utils.clip_grad_norm_ / clip_grad_value_
+ * as Lightning's Trainer applies them for gradient_clip_val / gradient_clip_algorithm
+ * (configs/experiment/baseline_only_imaging/baseline_only_imaging_vit_base_16_only_100_samples.yaml:16).
+ * No host synchronisation and no atomics: every sum has a fixed order, so the norm and the
+ * step that uses it are bitwise reproducible.
+ *
+ * vlp_grad_sumsq: partials[s] = sum of g[i]^2 (squares and sums in fp64) over segment s of the
+ * span, elements [16384 s, 16384 (s + 1)); *nparts (host memory, written during the call) =
+ * ceil(n / 16384), a function of n alone, so several spans can be laid end to end in one
+ * partials buffer.  g needs only 4-B alignment.  n <= 0: *nparts = 0, nothing launched, returns 0;
+ * a NULL pointer: hipErrorInvalidValue, nothing launched.
+ * vlp_grad_sumsq_nparts: the same count without a launch (to size the partials buffer). */
+int vlp_grad_sumsq_nparts(long long n, int* nparts);
+int vlp_grad_sumsq(long long n, const float* g, double* partials, int* nparts, void* stream);
+/* one workgroup: out[0] = (float)sqrt(sum of partials[0 .. nparts)) (fp64 sum, fixed order),
+ * out[1] = min(1, max_norm / (out[0] + 1e-6f)): clip_grad_norm_'s total_norm and clamped
+ * coefficient (error_if_nonfinite=False: non-finite values propagate as in torch) */
+int vlp_clip_coef(int nparts, const double* partials, float max_norm, float* out, void* stream);
+/* vlp_adamw on the clipped gradient gi, which is also stored back to g (what torch leaves in
+ * p.grad).  mode 1: gi = g[i] * coef[0], coef a DEVICE pointer (vlp_clip_coef's out + 1);
+ * mode 2: gi = clamp(g[i], -clip_value, clip_value) (gradient_clip_algorithm: value).
+ * The update after that is vlp_adamw's; with coef[0] == 1 the results are its bits. */
+int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                   float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                   const float* coef, float clip_value, void* stream);
 int vlp_pack_conv(int dtype, int Co, int C, int KH, int KW, const float* w, void* wp, void* wt,
                   void* stream);
 /* vlp_pack_conv for n <= 48 convolutions in one launch: desc holds n rows of

@@ -27,6 +27,101 @@ __global__ void adamw_kernel(size_t n, float* __restrict__ p, const float* __res
   }
 }
 
+// Gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, Lightning's
+// gradient_clip_val) on the device, with no host read-back and no atomics:
+//   grad_sumsq_kernel  fp64 sum of g^2 per fixed-length segment of a span -> partials
+//   clip_coef_kernel   one workgroup: norm = sqrt(sum of all partials), coef = min(1, max / (norm + 1e-6))
+//   adamw_clip_kernel  adamw_kernel on gi = g * coef (MODE 1) or clamp(g, +-clip_value) (MODE 2),
+//                      gi written back to g
+// A span's segment s is its elements [s * kSumsqSeg, (s + 1) * kSumsqSeg): the partials are a
+// function of the span alone, not of the grid or the CU count, and every sum below has a fixed
+// order, so a rerun reproduces the norm bit for bit.
+constexpr int kSumsqSeg = 16384;   // elements per partial (a multiple of 4: every segment of a span
+                                   // has the span's 16-B misalignment)
+
+// sum over the 256 threads of a workgroup, fixed order; valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();   // red may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__device__ __forceinline__ double sq_f64(float x) { return (double)x * (double)x; }   // exact
+
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(size_t n, const float* __restrict__ g,
+                                                         double* __restrict__ partials, int nparts) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  // elements in front of the first 16-B boundary (spans start anywhere in an arena)
+  const int mis = (int)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+  for (int s = blockIdx.x; s < nparts; s += gridDim.x) {
+    const float* seg = g + (size_t)s * kSumsqSeg;
+    const size_t left = n - (size_t)s * kSumsqSeg;
+    const int len = left < (size_t)kSumsqSeg ? (int)left : kSumsqSeg;
+    const int head = mis < len ? mis : len;
+    const int nvec = (len - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+    if (tid < head) a0 = sq_f64(seg[tid]);
+    const float4* body = reinterpret_cast<const float4*>(seg + head);
+#pragma unroll 4
+    for (int i = tid; i < nvec; i += 256) {
+      const float4 q = body[i];
+      a0 += sq_f64(q.x);
+      a1 += sq_f64(q.y);
+      a2 += sq_f64(q.z);
+      a3 += sq_f64(q.w);
+    }
+    if (tail0 + tid < len) a1 += sq_f64(seg[tail0 + tid]);
+    const double t = block_sum_f64((a0 + a1) + (a2 + a3), red);
+    if (tid == 0) partials[s] = t;
+  }
+}
+
+__global__ void __launch_bounds__(256) clip_coef_kernel(int nparts, const double* __restrict__ partials,
+                                                        float max_norm, float* __restrict__ out) {
+  __shared__ double red[4];
+  double a = 0.;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += partials[i];
+  const double t = block_sum_f64(a, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(t);
+    const float c = max_norm / (norm + 1e-6f);
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;   // torch.clamp(c, max=1): a NaN stays a NaN
+  }
+}
+
+template <int MODE>
+__global__ void adamw_clip_kernel(size_t n, float* __restrict__ p, float* __restrict__ g,
+                                  float* __restrict__ m, float* __restrict__ v, float lr, float b1,
+                                  float b2, float eps, float wd, float step_size, float bc2_sqrt,
+                                  const float* __restrict__ coef, float clip_value) {
+  const float c = MODE == 1 ? coef[0] : 0.f;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    float pi = p[i] * (1.f - lr * wd);
+    float gi = g[i];
+    if (MODE == 1) {
+      gi = gi * c;
+      // torch rounds the clipped gradient to fp32 before AdamW reads it: the empty asm
+      // keeps the product from being contracted into the multiply-adds below
+      asm("" : "+v"(gi));
+    } else {
+      gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
+    }
+    g[i] = gi;
+    float mi = fmaf(1.f - b1, gi - m[i], m[i]);   // torch exp_avg.lerp_(grad, 1-beta1)
+    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    float denom = sqrtf(vi) / bc2_sqrt + eps;
+    p[i] = pi - step_size * (mi / denom);
+  }
+}
+
 template <typename T>
 __global__ void pack_conv_kernel(int Co, int C, int KH, int KW, const float* __restrict__ w,
                                  T* __restrict__ wp, T* __restrict__ wt) {
@@ -188,6 +283,48 @@ VLP_EXPORT int vlp_adamw(long long n, float* p, const float* g, float* m, float*
   if (n <= 0) return 0;
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n, p, g,
                      m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt);
+  return (int)hipGetLastError();
+}
+
+// partials of an n-element span: a function of n alone (host side, no GPU work)
+VLP_EXPORT int vlp_grad_sumsq_nparts(long long n, int* nparts) {
+  if (!nparts || n > (long long)kSumsqSeg * 0x7fffffffll) return (int)hipErrorInvalidValue;
+  *nparts = n <= 0 ? 0 : (int)((n + kSumsqSeg - 1) / kSumsqSeg);
+  return 0;
+}
+
+VLP_EXPORT int vlp_grad_sumsq(long long n, const float* g, double* partials, int* nparts, void* stream) {
+  int np = 0;
+  if (int e = vlp_grad_sumsq_nparts(n, &np)) return e;
+  if (nparts) *nparts = np;
+  if (n <= 0) return 0;
+  if (!g || !partials || !nparts) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(np < 2048 ? np : 2048), dim3(256), 0, (hipStream_t)stream,
+                     (size_t)n, g, partials, np);
+  return (int)hipGetLastError();
+}
+
+VLP_EXPORT int vlp_clip_coef(int nparts, const double* partials, float max_norm, float* out, void* stream) {
+  if (nparts < 0 || !out || (nparts > 0 && !partials)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nparts, partials,
+                     max_norm, out);
+  return (int)hipGetLastError();
+}
+
+// vlp_adamw on the clipped gradient, which is also written back to g.
+// mode 1: g * coef[0] (coef on the device: vlp_clip_coef's out + 1); mode 2: clamp(g, +-clip_value)
+VLP_EXPORT int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                              float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                              const float* coef, float clip_value, void* stream) {
+  if ((mode != 1 && mode != 2) || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
+  if (mode == 1)
+    hipLaunchKernelGGL(adamw_clip_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
+                       p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value);
+  else
+    hipLaunchKernelGGL(adamw_clip_kernel<2>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
+                       p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value);
   return (int)hipGetLastError();
 }
 

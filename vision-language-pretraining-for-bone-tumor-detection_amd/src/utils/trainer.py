@@ -245,9 +245,19 @@ class Trainer:
                  devices="auto", log_every_n_steps: int = 1, max_steps: int = -1,
                  limit_train_batches: Optional[int] = None, limit_val_batches: Optional[int] = None,
                  callbacks: Optional[List] = None, logger=None, enable_checkpointing: bool = True,
-                 default_root_dir: Optional[str] = None, check_val_every_n_epoch: int = 1, **unused):
+                 default_root_dir: Optional[str] = None, check_val_every_n_epoch: int = 1,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = None,
+                 **unused):
         if max_epochs is not None and min_epochs is not None and min_epochs > max_epochs:
             raise ValueError("min_epochs > max_epochs")
+        # Lightning's gradient_clip_val / gradient_clip_algorithm (None -> "norm");
+        # None or a value <= 0: no clipping, as there
+        algo = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
+        if algo not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        clip = None if gradient_clip_val is None else float(gradient_clip_val)
+        self.gradient_clip_val = clip if clip is not None and clip > 0 else None
+        self.gradient_clip_algorithm = algo
         self.min_epochs, self.max_epochs = min_epochs, max_epochs
         self.accelerator, self.devices = accelerator, devices
         self.log_every_n_steps = max(1, int(log_every_n_steps))
@@ -315,8 +325,25 @@ class Trainer:
             p.grad.copy_(flat[off:off + n].view_as(p.grad))
             off += n
 
-    def _log(self, model, step_loss):
+    def _clip_gradients(self, model):
+        """torch.nn.utils.clip_grad_norm_ / clip_grad_value_ over the model's parameters that
+        have gradients, as Lightning applies gradient_clip_val between backward and the
+        optimizer step (the path for optimizers without a fused clip).  Returns the total
+        norm before clipping (a tensor; None for "value" or with clipping off)."""
+        if self.gradient_clip_val is None:
+            return None
+        params = [p for p in model.parameters() if p.grad is not None]
+        if not params:
+            return None
+        if self.gradient_clip_algorithm == "value":
+            torch.nn.utils.clip_grad_value_(params, self.gradient_clip_val)
+            return None
+        return torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
+
+    def _log(self, model, step_loss, grad_norm=None):
         rec = {"step": self.global_step, "epoch": self.current_epoch, "train/loss": float(step_loss)}
+        if grad_norm is not None:
+            rec["grad_norm"] = float(grad_norm.detach())   # read back at logging steps only
         for k, v in getattr(model, "logged", {}).items():
             if torch.is_tensor(v) and v.numel() == 1:
                 rec[k] = float(v.detach())
@@ -336,6 +363,11 @@ class Trainer:
         optimizer = conf["optimizer"] if isinstance(conf, dict) else conf
         sched = conf.get("lr_scheduler") if isinstance(conf, dict) else None
         self.optimizer = optimizer
+        # gradient clipping: fused into the optimizer's step where it can (FusedAdamW: norm,
+        # coefficient and scaling stay on the device), else torch's clip_grad_* before step()
+        fused_clip = hasattr(optimizer, "set_gradient_clipping")
+        if fused_clip:
+            optimizer.set_gradient_clipping(self.gradient_clip_val, self.gradient_clip_algorithm)
         dev = self._device(model)
         world = self._dp_world()
         reduce_grads = world > 1 and not getattr(model, "handles_dp_collectives", False)
@@ -360,13 +392,20 @@ class Trainer:
                 loss.backward()
                 if reduce_grads:
                     self.average_gradients(model, world)
+                # Under data parallelism every rank holds the all-reduced gradients by now
+                # (average_gradients above, or ClipStepFn.backward for modules that handle their
+                # own collectives), so each rank's local norm is the global norm: clipping adds
+                # no collective.
+                grad_norm = None if fused_clip else self._clip_gradients(model)
                 optimizer.step()
+                if fused_clip:
+                    grad_norm = optimizer.last_grad_norm
                 self.global_step += 1
                 if self.global_step % self.log_every_n_steps == 0:
                     lv = loss.detach().item()
                     if not math.isfinite(lv):
                         raise FloatingPointError(f"non-finite loss {lv} at step {self.global_step}")
-                    self._log(model, lv)
+                    self._log(model, lv, grad_norm)
                 self.step_times.append(time.perf_counter() - t0)
                 if 0 < self.max_steps <= self.global_step:
                     stop = True

@@ -604,6 +604,46 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
                     float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5), _s())
 
 
+def grad_sumsq_nparts(n):
+    """Number of fp64 partials vlp_grad_sumsq writes for an n-element span."""
+    import ctypes
+    k = ctypes.c_int(0)
+    lib().vlp_grad_sumsq_nparts(int(n), ctypes.byref(k))
+    return k.value
+
+
+def grad_sumsq(g, partials, offset=0):
+    """fp64 partial sums of g^2 into partials[offset:]; returns how many were written
+    (replaces the per-tensor norms of torch.nn.utils.clip_grad_norm_)."""
+    import ctypes
+    if g.dtype != torch.float32 or partials.dtype != torch.float64 or not g.is_contiguous():
+        raise TypeError("grad_sumsq: contiguous fp32 gradients and fp64 partials")
+    if offset < 0 or offset + grad_sumsq_nparts(g.numel()) > partials.numel():
+        raise ValueError("grad_sumsq: partials buffer too small")
+    k = ctypes.c_int(0)
+    lib().vlp_grad_sumsq(g.numel(), ptr(g), ptr(partials[offset:]), ctypes.byref(k), _s())
+    return k.value
+
+
+def clip_coef(nparts, partials, max_norm, out):
+    """out[0] = global gradient norm, out[1] = min(1, max_norm / (norm + 1e-6)) (fp32 [2])."""
+    if nparts > partials.numel() or out.numel() < 2 or out.dtype != torch.float32 or partials.dtype != torch.float64:
+        raise ValueError("clip_coef: nparts fp64 partials and an fp32 [2] output")
+    lib().vlp_clip_coef(int(nparts), ptr(partials), float(max_norm), ptr(out), _s())
+
+
+def adamw_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, coef=None, clip_value=None):
+    """adamw on the clipped gradient (written back to g): g * coef[0] with coef a device
+    fp32 tensor (norm clipping), else clamp(g, -clip_value, clip_value)."""
+    if (coef is None) == (clip_value is None):
+        raise ValueError("adamw_clip: exactly one of coef / clip_value")
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    lib().vlp_adamw_clip(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
+                         float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
+                         1 if coef is not None else 2, ptr(coef), float(clip_value or 0.0), _s())
+
+
 def pack_conv(w, wp, wt):
     Co, C, KH, KW = w.shape
     ref = wp if wp is not None else wt

@@ -14,6 +14,15 @@ offsets as the parameters), and `self.state[p]` holds {"step", "exp_avg",
 "exp_avg_sq"} with the moments as views of those buffers -- torch.optim.AdamW's
 layout, so `state_dict()` / `load_state_dict()` round-trip (and a torch AdamW
 state dict loads here) while the update stays one launch per span.
+
+Gradient clipping (`set_gradient_clipping`, Lightning's gradient_clip_val /
+gradient_clip_algorithm) is fused into the step and never reads the device back.
+"norm" is torch.nn.utils.clip_grad_norm_ over every parameter that has a gradient,
+across all groups: one `vlp_grad_sumsq` per span into one fp64 partials buffer,
+one `vlp_clip_coef`, then `vlp_adamw_clip` per span scales the gradient by the
+device-side coefficient, writes it back and updates.  "value" is clip_grad_value_:
+`vlp_adamw_clip` clamps instead, with no norm pass.  Off (the default), the step
+launches `vlp_adamw` only.
 """
 from __future__ import annotations
 
@@ -42,6 +51,27 @@ class FusedAdamW(torch.optim.Optimizer):
         self._flat = {}        # id(arena) -> (m, v) flat fp32 buffers
         self._span_cache = {}
         self._steps = {}       # id(p) -> step count (mirrored into state[p]["step"] by state_dict())
+        self._clip = None      # None | ("norm", max_norm) | ("value", clip_value)
+        self._clip_bufs = None  # (fp64 partials, fp32 {norm, coef}) on the arenas' device
+        self._copied = []      # (p.grad, arena view) pairs _spans copied in this step
+        self.last_grad_norm = None   # device scalar: the global norm before clipping ("norm" only)
+
+    def set_gradient_clipping(self, val, algorithm="norm"):
+        """Clip in every later step(): "norm" to a global L2 norm of `val`
+        (clip_grad_norm_), "value" each element to [-val, val] (clip_grad_value_).
+        None or val <= 0 turns clipping off."""
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"FusedAdamW: gradient clip algorithm must be 'norm' or 'value', got {algorithm!r}")
+        self._clip = None if val is None or val <= 0 else (algorithm, float(val))
+        self.last_grad_norm = None
+
+    def _clip_buffers(self, device, nparts):
+        b = self._clip_bufs
+        if b is None or b[0].device != device or b[0].numel() < nparts:
+            out = b[1] if b is not None and b[1].device == device else torch.zeros(2, dtype=torch.float32, device=device)
+            b = (torch.empty(max(nparts, 1), dtype=torch.float64, device=device), out)
+            self._clip_bufs = b
+        return b
 
     def _moments(self, arena):
         b = self._flat.get(id(arena))
@@ -74,6 +104,8 @@ class FusedAdamW(torch.optim.Optimizer):
             g = arena.grad[o:o + n].view_as(p)
             if p.grad.data_ptr() != g.data_ptr():
                 g.copy_(p.grad)  # gradients not produced in place (e.g. accumulated by autograd)
+                if self._clip is not None:
+                    self._copied.append((p.grad, g))   # step() copies the clipped gradient back
             items.append((arena, o, n, p))
         sig = tuple(t[1] for t in items) + tuple(id(t[0]) for t in items)
         cached = self._span_cache.get(sig)
@@ -104,9 +136,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            for arena, o, n, ps in self._spans(group):
+        # every group's spans first: the norm covers all of them before any update
+        self._copied = []
+        work = [(group, self._spans(group)) for group in self.param_groups]
+        if self._clip is not None and self._clip[0] == "norm":
+            self._launch_norm([s for _, spans in work for s in spans])
+        for group, spans in work:
+            for arena, o, n, ps in spans:
                 steps = set()
                 for p in ps:
                     if id(p) not in self._steps:
@@ -121,13 +157,35 @@ class FusedAdamW(torch.optim.Optimizer):
                         self._launch(arena, po, pn, group, self._steps[id(p)])
                     continue
                 self._launch(arena, o, n, group, steps.pop())
+        for grad, g in self._copied:   # p.grad outside the arena: leave it clipped as well
+            grad.copy_(g)
+        self._copied = []
         return loss
+
+    def _launch_norm(self, spans):
+        """Global gradient norm and clip coefficient of the step, on the device."""
+        if not spans:
+            self.last_grad_norm = None
+            return
+        total = sum(ops.grad_sumsq_nparts(n) for _, _, n, _ in spans)
+        partials, out = self._clip_buffers(spans[0][0].grad.device, total)
+        off = 0
+        for arena, o, n, _ in spans:
+            off += ops.grad_sumsq(arena.grad[o:o + n], partials, off)
+        ops.clip_coef(off, partials, self._clip[1], out)
+        self.last_grad_norm = out[0]
 
     def _launch(self, arena, o, n, group, step):
         b1, b2 = group["betas"]
         m, v = self._moments(arena)
-        ops.adamw(arena.data[o:o + n], arena.grad[o:o + n], m[o:o + n], v[o:o + n],
-                  group["lr"], b1, b2, group["eps"], group["weight_decay"], step)
+        args = (arena.data[o:o + n], arena.grad[o:o + n], m[o:o + n], v[o:o + n],
+                group["lr"], b1, b2, group["eps"], group["weight_decay"], step)
+        if self._clip is None:
+            ops.adamw(*args)
+        elif self._clip[0] == "norm":
+            ops.adamw_clip(*args, coef=self._clip_bufs[1][1:])
+        else:
+            ops.adamw_clip(*args, clip_value=self._clip[1])
 
     def state_dict(self):
         for group in self.param_groups:
