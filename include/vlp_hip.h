@@ -551,6 +551,30 @@ int vlp_clip_coef(int nparts, const double* partials, float max_norm, float* out
 int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
                    float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
                    const float* coef, float clip_value, void* stream);
+/* Gradient accumulation on the device (Lightning's accumulate_grad_batches): the backward
+ * overwrites the flat gradient arena, so the micro-batches of one optimizer step are summed in
+ * an accumulator of the same layout.  Same conventions as above: no host synchronisation, no
+ * atomics, bitwise reproducible; 16-B vector accesses where the operands share their 16-B
+ * misalignment (spans at equal offsets of equally laid out arenas do), scalar ones otherwise;
+ * every pointer needs 4-B alignment (hipErrorInvalidValue if not, or if NULL with n > 0);
+ * n <= 0 launches nothing.
+ *
+ * vlp_grad_accum: acc[i] = (first ? 0 : acc[i]) + w * g[i], one fused multiply-add per element.
+ * first != 0 does not read acc, which may hold anything (no memset is needed).
+ * vlp_grad_accum_sumsq: vlp_grad_sumsq of s[i] = fmaf(w, g[i], acc[i]), the accumulated gradient
+ * including a last micro-batch that is never stored; same segments, partials layout and *nparts,
+ * so vlp_clip_coef consumes the partials unchanged.
+ * vlp_adamw_clip_accum: the vlp_adamw update on the gradient s[i] = fmaf(w, g[i], acc[i]) (the
+ * value vlp_grad_accum_sumsq squared), after mode 1: s * coef[0], mode 2: clamp(s, +-clip_value),
+ * mode 0: nothing.  One pass reads p, g, acc, m, v and writes p, m, v; g and acc are left alone.
+ * acc == NULL: vlp_adamw_clip with the same arguments, bit for bit (g written back, modes 1 / 2). */
+int vlp_grad_accum(long long n, float* acc, const float* g, float w, int first, void* stream);
+int vlp_grad_accum_sumsq(long long n, const float* acc, const float* g, float w, double* partials,
+                         int* nparts, void* stream);
+int vlp_adamw_clip_accum(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                         float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                         const float* coef, float clip_value, const float* acc, float w,
+                         void* stream);
 int vlp_pack_conv(int dtype, int Co, int C, int KH, int KW, const float* w, void* wp, void* wt,
                   void* stream);
 /* vlp_pack_conv for n <= 48 convolutions in one launch: desc holds n rows of

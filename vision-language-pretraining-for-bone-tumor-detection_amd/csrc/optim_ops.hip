@@ -10,6 +10,8 @@
 // GEMM operand layouts of conv_ops.hip, and the weight-gradient workspaces back.
 #include "common.h"
 
+#include <initializer_list>
+
 namespace vlp {
 
 __global__ void adamw_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g,
@@ -119,6 +121,138 @@ __global__ void adamw_clip_kernel(size_t n, float* __restrict__ p, float* __rest
     v[i] = vi;
     float denom = sqrtf(vi) / bc2_sqrt + eps;
     p[i] = pi - step_size * (mi / denom);
+  }
+}
+
+// Gradient accumulation (Lightning's accumulate_grad_batches) over the flat arenas.  The
+// backward overwrites the gradient arena, so every micro-batch but the last of an optimizer
+// step is folded into an accumulator of the same layout, and the last one is folded in by
+// the step itself:
+//   grad_accum_kernel        acc = (FIRST ? 0 : acc) + w g            one pass, 3 (FIRST: 2) streams
+//   grad_accum_sumsq_kernel  grad_sumsq_kernel on fmaf(w, g, acc)     the accumulated gradient's norm
+//   adamw_accum_kernel       adamw_clip_kernel on fmaf(w, g, acc)     nothing written back to g / acc
+// fmaf(w, g, acc) is one rounding; the norm kernel and the step form it with the same
+// instruction from the same operands, so the norm is that of the gradient the step uses.
+// Spans start anywhere in an arena: `head` elements in front of the first 16-B boundary are
+// scalar, then 16-B vectors, then a scalar tail.  Operands that do not share their 16-B
+// misalignment (never the case for spans of equally laid out arenas) take head = n: all scalar.
+__host__ __device__ __forceinline__ int vec_head(const void* a) { return (int)(((16 - ((uintptr_t)a & 15)) & 15) >> 2); }
+
+template <bool FIRST>
+__global__ void __launch_bounds__(256) grad_accum_kernel(size_t n, float* __restrict__ acc,
+                                                         const float* __restrict__ g, float w, size_t head) {
+  const size_t nvec = (n - head) >> 2;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+  const float4* g4 = reinterpret_cast<const float4*>(g + head);
+  float4* a4 = reinterpret_cast<float4*>(acc + head);
+  for (size_t i = tid; i < nvec; i += nthr) {
+    const float4 q = g4[i];
+    float4 a;
+    if (FIRST) {
+      a.x = w * q.x; a.y = w * q.y; a.z = w * q.z; a.w = w * q.w;
+    } else {
+      a = a4[i];
+      a.x = fmaf(w, q.x, a.x); a.y = fmaf(w, q.y, a.y); a.z = fmaf(w, q.z, a.z); a.w = fmaf(w, q.w, a.w);
+    }
+    a4[i] = a;
+  }
+  // the head and what follows the vectors (at most 3 + 3 elements unless all scalar)
+  const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
+  for (size_t j = tid; j < nsc; j += nthr) {
+    const size_t i = j < head ? j : tail0 + (j - head);
+    acc[i] = FIRST ? w * g[i] : fmaf(w, g[i], acc[i]);
+  }
+}
+
+// grad_sumsq_kernel's segments and reduction order on s = fmaf(w, g, acc); vec = 0: scalar loads
+__global__ void __launch_bounds__(256) grad_accum_sumsq_kernel(size_t n, const float* __restrict__ acc,
+                                                               const float* __restrict__ g, float w,
+                                                               double* __restrict__ partials, int nparts, int vec) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const int mis = vec_head(g);
+  for (int s = blockIdx.x; s < nparts; s += gridDim.x) {
+    const size_t base = (size_t)s * kSumsqSeg;
+    const float* gs = g + base;
+    const float* as = acc + base;
+    const size_t left = n - base;
+    const int len = left < (size_t)kSumsqSeg ? (int)left : kSumsqSeg;
+    const int head = vec ? (mis < len ? mis : len) : len;
+    const int nvec = (len - head) >> 2;
+    const int tail0 = head + 4 * nvec;
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+    for (int i = tid; i < head; i += 256) a0 += sq_f64(fmaf(w, gs[i], as[i]));
+    const float4* gb = reinterpret_cast<const float4*>(gs + head);
+    const float4* ab = reinterpret_cast<const float4*>(as + head);
+#pragma unroll 4
+    for (int i = tid; i < nvec; i += 256) {
+      const float4 q = gb[i], a = ab[i];
+      a0 += sq_f64(fmaf(w, q.x, a.x));
+      a1 += sq_f64(fmaf(w, q.y, a.y));
+      a2 += sq_f64(fmaf(w, q.z, a.z));
+      a3 += sq_f64(fmaf(w, q.w, a.w));
+    }
+    if (tail0 + tid < len) a1 += sq_f64(fmaf(w, gs[tail0 + tid], as[tail0 + tid]));
+    const double t = block_sum_f64((a0 + a1) + (a2 + a3), red);
+    if (tid == 0) partials[s] = t;
+  }
+}
+
+// MODE 0: no clipping, 1: * coef[0], 2: clamp(+-clip_value), as adamw_clip_kernel
+template <int MODE>
+__device__ __forceinline__ void adamw_accum_update(float& p, float g, float a, float& m, float& v, float w, float lr,
+                                                   float b1, float b2, float eps, float wd, float step_size,
+                                                   float bc2_sqrt, float c, float clip_value) {
+  float pi = p * (1.f - lr * wd);
+  float gi = fmaf(w, g, a);
+  // the accumulated gradient is an fp32 value of its own (torch's p.grad after the last
+  // backward), as is the clipped one: the empty asm keeps each from being contracted further
+  asm("" : "+v"(gi));
+  if (MODE == 1) {
+    gi = gi * c;
+    asm("" : "+v"(gi));
+  } else if (MODE == 2) {
+    gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
+  }
+  float mi = fmaf(1.f - b1, gi - m, m);   // torch exp_avg.lerp_(grad, 1-beta1)
+  float vi = v * b2 + (1.f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = pi - step_size * (mi / denom);
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) adamw_accum_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g,
+                                                          const float* __restrict__ acc, float* __restrict__ m,
+                                                          float* __restrict__ v, float w, float lr, float b1, float b2,
+                                                          float eps, float wd, float step_size, float bc2_sqrt,
+                                                          const float* __restrict__ coef, float clip_value,
+                                                          size_t head) {
+  const float c = MODE == 1 ? coef[0] : 0.f;
+  const size_t nvec = (n - head) >> 2;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+  float4* p4 = reinterpret_cast<float4*>(p + head);
+  float4* m4 = reinterpret_cast<float4*>(m + head);
+  float4* v4 = reinterpret_cast<float4*>(v + head);
+  const float4* g4 = reinterpret_cast<const float4*>(g + head);
+  const float4* a4 = reinterpret_cast<const float4*>(acc + head);
+  for (size_t i = tid; i < nvec; i += nthr) {
+    float4 pp = p4[i], mm = m4[i], vv = v4[i];
+    const float4 gg = g4[i], aa = a4[i];
+    adamw_accum_update<MODE>(pp.x, gg.x, aa.x, mm.x, vv.x, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE>(pp.y, gg.y, aa.y, mm.y, vv.y, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE>(pp.z, gg.z, aa.z, mm.z, vv.z, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE>(pp.w, gg.w, aa.w, mm.w, vv.w, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    m4[i] = mm;
+    v4[i] = vv;
+    p4[i] = pp;
+  }
+  const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
+  for (size_t j = tid; j < nsc; j += nthr) {
+    const size_t i = j < head ? j : tail0 + (j - head);
+    adamw_accum_update<MODE>(p[i], g[i], acc[i], m[i], v[i], w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c,
+                             clip_value);
   }
 }
 
@@ -325,6 +459,76 @@ VLP_EXPORT int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* 
   else
     hipLaunchKernelGGL(adamw_clip_kernel<2>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
                        p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value);
+  return (int)hipGetLastError();
+}
+
+// scalar elements in front of the 16-B vectors of an n-element span: the operands' common
+// misalignment, or n (all scalar) when they do not share one
+static inline size_t common_head(size_t n, std::initializer_list<const void*> ptrs) {
+  const int h = vec_head(*ptrs.begin());
+  for (const void* q : ptrs)
+    if (vec_head(q) != h) return n;
+  return (size_t)h < n ? (size_t)h : n;
+}
+
+// blocks of 256 threads for a 16-B-vector grid-stride loop over n floats
+static inline int vec_grid_for(size_t n) {
+  size_t b = (n / 4 + 255) / 256;
+  if (b > 2048) b = 2048;
+  if (b < 1) b = 1;
+  return (int)b;
+}
+
+VLP_EXPORT int vlp_grad_accum(long long n, float* acc, const float* g, float w, int first, void* stream) {
+  if (n <= 0) return 0;
+  if (!acc || !g || (((uintptr_t)acc | (uintptr_t)g) & 3)) return (int)hipErrorInvalidValue;
+  const size_t head = common_head((size_t)n, {acc, g});
+  if (first)
+    hipLaunchKernelGGL(grad_accum_kernel<true>, dim3(vec_grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
+                       acc, g, w, head);
+  else
+    hipLaunchKernelGGL(grad_accum_kernel<false>, dim3(vec_grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
+                       acc, g, w, head);
+  return (int)hipGetLastError();
+}
+
+VLP_EXPORT int vlp_grad_accum_sumsq(long long n, const float* acc, const float* g, float w, double* partials,
+                                    int* nparts, void* stream) {
+  int np = 0;
+  if (int e = vlp_grad_sumsq_nparts(n, &np)) return e;
+  if (nparts) *nparts = np;
+  if (n <= 0) return 0;
+  if (!acc || !g || !partials || !nparts || (((uintptr_t)acc | (uintptr_t)g) & 3)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_accum_sumsq_kernel, dim3(np < 2048 ? np : 2048), dim3(256), 0, (hipStream_t)stream,
+                     (size_t)n, acc, g, w, partials, np, vec_head(acc) == vec_head(g) ? 1 : 0);
+  return (int)hipGetLastError();
+}
+
+// vlp_adamw_clip on coef * (acc + w g) (mode 1), clamp(acc + w g) (mode 2) or acc + w g itself
+// (mode 0); neither g nor acc is written.  acc == NULL: vlp_adamw_clip, bit for bit.
+VLP_EXPORT int vlp_adamw_clip_accum(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                                    float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                                    const float* coef, float clip_value, const float* acc, float w, void* stream) {
+  if (!acc)
+    return vlp_adamw_clip(n, p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, mode, coef, clip_value,
+                          stream);
+  if (mode < 0 || mode > 2 || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) & 3) return (int)hipErrorInvalidValue;
+  const size_t head = common_head((size_t)n, {p, g, m, v, acc});
+  const dim3 grid(vec_grid_for(n)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define VLP_ACCUM_LAUNCH(MODE)                                                                                   \
+  hipLaunchKernelGGL(adamw_accum_kernel<MODE>, grid, block, 0, st, (size_t)n, p, (const float*)g, acc, m, v, w, lr, \
+                     beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value, head)
+  if (mode == 0)
+    VLP_ACCUM_LAUNCH(0);
+  else if (mode == 1)
+    VLP_ACCUM_LAUNCH(1);
+  else
+    VLP_ACCUM_LAUNCH(2);
+#undef VLP_ACCUM_LAUNCH
   return (int)hipGetLastError();
 }
 

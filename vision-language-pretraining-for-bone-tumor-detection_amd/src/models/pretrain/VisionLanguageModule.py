@@ -371,7 +371,10 @@ class VisionLanguageModule(_Base):
 
     def _towers(self):
         m = types.SimpleNamespace(image_tower=self.image_encoder.model, text_tower=self.text_encoder.model,
-                                  head=self._head, training=self.training)
+                                  head=self._head, training=self.training,
+                                  # set by the Trainer under gradient accumulation with data parallelism:
+                                  # the optimizer all-reduces the accumulated gradient once per step
+                                  defer_grad_reduce=getattr(self, "defer_grad_reduce", False))
         return m
 
     def _all_params(self):

@@ -17,6 +17,13 @@ would: the module's `all_reduce_gradients()` when it has one (one RCCL call
 over the ResNet34 tower's flat gradient arena), else one flat SUM all-reduce
 over every gradient, divided by the world size.
 
+`accumulate_grad_batches` = k (Lightning's semantics): each micro-batch's loss is
+scaled by 1 / k; the optimizer, a step-interval scheduler and `global_step`
+advance once per k batches, and once more for what an epoch leaves of a group;
+gradients are clipped and, under data parallelism, all-reduced once per
+optimizer step, accumulated.  FusedAdamW accumulates on the device (its
+`accumulate()`), torch optimizers through autograd.
+
 Callbacks (the Lightning ones the reference configs name resolve here when
 Lightning is absent, src/utils/config.py): ModelCheckpoint (best-k by a
 monitored metric, Lightning checkpoint dict {state_dict, hyper_parameters,
@@ -247,9 +254,14 @@ class Trainer:
                  callbacks: Optional[List] = None, logger=None, enable_checkpointing: bool = True,
                  default_root_dir: Optional[str] = None, check_val_every_n_epoch: int = 1,
                  gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = None,
-                 **unused):
+                 accumulate_grad_batches: int = 1, **unused):
         if max_epochs is not None and min_epochs is not None and min_epochs > max_epochs:
             raise ValueError("min_epochs > max_epochs")
+        # Lightning's accumulate_grad_batches: a positive integer (bool is not one)
+        k = accumulate_grad_batches
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate_grad_batches = k
         # Lightning's gradient_clip_val / gradient_clip_algorithm (None -> "norm");
         # None or a value <= 0: no clipping, as there
         algo = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
@@ -372,6 +384,54 @@ class Trainer:
         world = self._dp_world()
         reduce_grads = world > 1 and not getattr(model, "handles_dp_collectives", False)
         stop = False
+        # Gradient accumulation (accumulate_grad_batches = k > 1): every micro-batch's loss is
+        # scaled by 1 / k and one optimizer step is taken per k batches, or at the end of an
+        # epoch for what is left of a group.  Torch optimizers accumulate in p.grad through
+        # autograd (zero_grad only after a step).  An optimizer with `accumulate` (FusedAdamW,
+        # whose gradient arenas every backward overwrites) folds each micro-batch but the k-th
+        # into its accumulators on the device and its step() takes the k-th with them.
+        k = self.accumulate_grad_batches
+        fused_accum = k > 1 and hasattr(optimizer, "accumulate")
+        if fused_accum and reduce_grads:
+            raise ValueError("accumulate_grad_batches > 1 with an accumulating optimizer needs a module that "
+                             "handles its data-parallel collectives (handles_dp_collectives)")
+        if fused_accum and not fused_clip and self.gradient_clip_val is not None:
+            raise ValueError("accumulate_grad_batches > 1: the accumulating optimizer must clip its own gradients")
+        # Data parallelism: one gradient all-reduce per optimizer step, over the accumulated
+        # gradient.  A module that reduces inside its backward is told to leave the arenas local;
+        # then all k micro-batches are folded and the optimizer all-reduces its accumulators.
+        defer = fused_accum and _dist_on() and getattr(model, "handles_dp_collectives", False)
+        if fused_accum:
+            model.defer_grad_reduce = defer
+        step_sched = None            # a scheduler stepped per optimizer step (Lightning's interval: step)
+        if isinstance(sched, dict) and sched.get("interval", "epoch") == "step":
+            step_sched, sched = sched, None
+
+        def optimizer_step(loss, micro, folded):
+            """The step that ends a group of `micro` micro-batches; folded: all of them are in
+            the optimizer's accumulators already (the remainder of an epoch)."""
+            if fused_accum and defer:
+                if not folded:
+                    optimizer.accumulate(1.0, first=micro == 1)
+                optimizer.reduce_accumulated()
+            elif reduce_grads:
+                self.average_gradients(model, world)
+            # Under data parallelism every rank holds the all-reduced gradients by now
+            # (above, or ClipStepFn.backward for modules that handle their own collectives),
+            # so each rank's local norm is the global norm: clipping adds no collective.
+            grad_norm = None if fused_clip else self._clip_gradients(model)
+            optimizer.step()
+            if fused_clip:
+                grad_norm = optimizer.last_grad_norm
+            self.global_step += 1
+            if step_sched is not None and self.global_step % max(1, int(step_sched.get("frequency", 1))) == 0:
+                step_sched["scheduler"].step()
+            if self.global_step % self.log_every_n_steps == 0:
+                lv = loss.detach().item()
+                if not math.isfinite(lv):
+                    raise FloatingPointError(f"non-finite loss {lv} at step {self.global_step}")
+                self._log(model, lv, grad_norm)
+
         # training-batch augmentation on the device (the reference's MONAI chain runs
         # in its DataLoader workers, PretrainDataModule.py:186-198)
         augment = getattr(datamodule, "device_augment", None) if datamodule is not None else None
@@ -381,35 +441,31 @@ class Trainer:
             model.train()
             if hasattr(model, "on_train_epoch_start"):
                 model.on_train_epoch_start()
+            micro, loss = 0, None     # micro-batches since the last optimizer step
             for i, batch in enumerate(DevicePrefetcher(train_dataloaders, dev)):
                 if self.limit_train_batches is not None and i >= self.limit_train_batches:
                     break
                 t0 = time.perf_counter()
                 if augment is not None:
                     batch = augment(batch)
-                optimizer.zero_grad(set_to_none=False)
+                if micro == 0:
+                    optimizer.zero_grad(set_to_none=False)
                 loss = model.training_step(batch, i)
-                loss.backward()
-                if reduce_grads:
-                    self.average_gradients(model, world)
-                # Under data parallelism every rank holds the all-reduced gradients by now
-                # (average_gradients above, or ClipStepFn.backward for modules that handle their
-                # own collectives), so each rank's local norm is the global norm: clipping adds
-                # no collective.
-                grad_norm = None if fused_clip else self._clip_gradients(model)
-                optimizer.step()
-                if fused_clip:
-                    grad_norm = optimizer.last_grad_norm
-                self.global_step += 1
-                if self.global_step % self.log_every_n_steps == 0:
-                    lv = loss.detach().item()
-                    if not math.isfinite(lv):
-                        raise FloatingPointError(f"non-finite loss {lv} at step {self.global_step}")
-                    self._log(model, lv, grad_norm)
+                (loss if k == 1 else loss / k).backward()
+                micro += 1
+                if micro < k:
+                    if fused_accum:
+                        optimizer.accumulate(1.0, first=micro == 1)
+                    self.step_times.append(time.perf_counter() - t0)
+                    continue
+                optimizer_step(loss, micro, False)
+                micro = 0
                 self.step_times.append(time.perf_counter() - t0)
                 if 0 < self.max_steps <= self.global_step:
                     stop = True
                     break
+            if micro > 0:    # the last, incomplete group of the epoch still steps
+                optimizer_step(loss, micro, fused_accum)
             if hasattr(model, "on_train_epoch_end"):
                 model.on_train_epoch_end()
             self._hook("on_train_epoch_end", model)

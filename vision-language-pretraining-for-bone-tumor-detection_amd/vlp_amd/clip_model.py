@@ -277,9 +277,12 @@ class ClipStepFn(torch.autograd.Function):
         # With the text stream the text backward and its collective also run
         # beside the image backward; every tensor crossing streams stays
         # referenced until the join below.
-        reducer = vdist.GradReducer()
+        # (`model.defer_grad_reduce`, gradient accumulation: the arenas are left local and the
+        # optimizer all-reduces the micro-batches' sum once per step)
+        deferred = bool(getattr(model, "defer_grad_reduce", False))
+        reducer = vdist.GradReducer(enabled=not deferred)
         on_stage = None
-        if vdist.active():
+        if vdist.active() and not deferred:
             def on_stage(off, n):
                 reducer.reduce_span(img_t.arena, off, n)
         s_txt = _text_stream(dcls.device)

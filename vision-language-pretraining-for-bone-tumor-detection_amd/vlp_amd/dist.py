@@ -106,17 +106,21 @@ class GradReducer:
     (layer4 -> stem, 52 / 27 / 4.5 / 0.9 MB) the moment their last weight
     gradient is folded, so all but the stem bucket overlap the rest of the
     backward (an RCCL collective runs on its own stream after the kernels
-    already queued on the current one).  `wait()` joins them."""
+    already queued on the current one).  `wait()` joins them.
 
-    def __init__(self):
+    enabled=False: nothing is reduced (gradient accumulation: the micro-batches'
+    sum is all-reduced once per optimizer step, FusedAdamW.reduce_accumulated)."""
+
+    def __init__(self, enabled: bool = True):
         self._work = []
+        self._enabled = enabled
 
     def reduce(self, arenas):
         for a in arenas:
             self.reduce_span(a, 0, a.grad.numel())
 
     def reduce_span(self, arena, off, n):
-        if n <= 0:
+        if n <= 0 or not self._enabled:
             return
         w = all_reduce_sum_(arena.grad[off:off + n], async_op=True)
         if w is not None:

@@ -644,6 +644,52 @@ def adamw_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, coef=None, clip_valu
                          1 if coef is not None else 2, ptr(coef), float(clip_value or 0.0), _s())
 
 
+def _f32_flat(name, *ts):
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError(f"{name}: contiguous fp32 tensors")
+    if any(t.numel() != ts[0].numel() for t in ts):
+        raise ValueError(f"{name}: operands of one length")
+
+
+def grad_accum(acc, g, w=1.0, first=False):
+    """acc = (0 if first else acc) + w * g; first=True never reads acc (gradient accumulation
+    over the flat arenas, whose backward overwrites g)."""
+    _f32_flat("grad_accum", acc, g)
+    lib().vlp_grad_accum(g.numel(), ptr(acc), ptr(g), float(w), 1 if first else 0, _s())
+
+
+def grad_accum_sumsq(acc, g, w, partials, offset=0):
+    """grad_sumsq of acc + w * g (which is not stored) into partials[offset:]; returns how many
+    partials were written."""
+    import ctypes
+    _f32_flat("grad_accum_sumsq", acc, g)
+    if partials.dtype != torch.float64:
+        raise TypeError("grad_accum_sumsq: fp64 partials")
+    if offset < 0 or offset + grad_sumsq_nparts(g.numel()) > partials.numel():
+        raise ValueError("grad_accum_sumsq: partials buffer too small")
+    k = ctypes.c_int(0)
+    lib().vlp_grad_accum_sumsq(g.numel(), ptr(acc), ptr(g), float(w), ptr(partials[offset:]), ctypes.byref(k), _s())
+    return k.value
+
+
+def adamw_clip_accum(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc, w=1.0, coef=None, clip_value=None):
+    """adamw on acc + w * g, scaled by coef[0] (device fp32, norm clipping), clamped to
+    +-clip_value, or as it is (neither given); g and acc are not written.  acc=None is
+    adamw_clip(p, g, ...), which needs one of coef / clip_value."""
+    if coef is not None and clip_value is not None:
+        raise ValueError("adamw_clip_accum: at most one of coef / clip_value")
+    if acc is None and coef is None and clip_value is None:
+        raise ValueError("adamw_clip_accum: without an accumulator one of coef / clip_value (else adamw)")
+    _f32_flat("adamw_clip_accum", p, g, m, v, *(() if acc is None else (acc,)))
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    mode = 1 if coef is not None else 2 if clip_value is not None else 0
+    lib().vlp_adamw_clip_accum(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
+                               float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
+                               mode, ptr(coef), float(clip_value or 0.0), ptr(acc), float(w), _s())
+
+
 def pack_conv(w, wp, wt):
     Co, C, KH, KW = w.shape
     ref = wp if wp is not None else wt

@@ -23,6 +23,17 @@ one `vlp_clip_coef`, then `vlp_adamw_clip` per span scales the gradient by the
 device-side coefficient, writes it back and updates.  "value" is clip_grad_value_:
 `vlp_adamw_clip` clamps instead, with no norm pass.  Off (the default), the step
 launches `vlp_adamw` only.
+
+Gradient accumulation (Lightning's accumulate_grad_batches): the towers' backward overwrites
+the gradient arenas, so `accumulate(w, first)` folds the micro-batch just run into an
+accumulator the size of each arena (`vlp_grad_accum`, one pass; the buffer is allocated by the
+first call and never cleared: `first` does not read it) and drops the .grad views, and the next
+`step()` takes what is pending: with fresh gradients in the arenas it steps on acc + w*g
+(`vlp_grad_accum_sumsq` for the norm, `vlp_adamw_clip_accum` for the update: the last
+micro-batch's sum is never stored), with none (every micro-batch folded, as under data
+parallelism, where `reduce_accumulated()` all-reduces the accumulators once per step) on the
+accumulator alone, through the kernels of the plain step.  Both clip modes act on the
+accumulated gradient.  Without `accumulate()` nothing changes and no buffer exists.
 """
 from __future__ import annotations
 
@@ -55,6 +66,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self._clip_bufs = None  # (fp64 partials, fp32 {norm, coef}) on the arenas' device
         self._copied = []      # (p.grad, arena view) pairs _spans copied in this step
         self.last_grad_norm = None   # device scalar: the global norm before clipping ("norm" only)
+        self._acc = {}         # id(arena) -> gradient accumulator (fp32, the arena's size), made by accumulate()
+        self._pending = None   # (signature, per-group spans) of the micro-batches folded since the last step
+        self._src = None       # gradient of the running step: None = arena.grad | ("sum", w) | ("acc",)
 
     def set_gradient_clipping(self, val, algorithm="norm"):
         """Clip in every later step(): "norm" to a global L2 norm of `val`
@@ -130,15 +144,77 @@ class FusedAdamW(torch.optim.Optimizer):
             return False
         return not any(end <= o < start for o, _, _ in arena.layout.values())
 
+    def _accumulator(self, arena):
+        b = self._acc.get(id(arena))
+        if b is None or b.numel() != arena.numel or b.device != arena.data.device:
+            b = torch.empty(arena.numel, dtype=torch.float32, device=arena.data.device)
+            self._acc[id(arena)] = b
+        return b
+
+    @staticmethod
+    def _signature(work):
+        return tuple((id(arena), o, n) for spans in work for arena, o, n, _ in spans)
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def accumulate(self, w=1.0, first=None):
+        """Fold the gradients of the backward just run into the accumulators: acc = w * g if
+        `first` (the accumulators' old contents are not read), else acc += w * g.  first=None:
+        whether anything is pending.  The .grad views are dropped, so the next backward writes
+        the arenas afresh; `step()` then uses what is pending."""
+        if first is None:
+            first = self._pending is None
+        copied, self._copied = self._copied, []
+        work = [self._spans(group) for group in self.param_groups]
+        self._copied = copied
+        sig = self._signature(work)
+        if not sig:
+            raise RuntimeError("FusedAdamW.accumulate: no parameter has a gradient")
+        if first:
+            self._pending = (sig, work)
+        elif self._pending is None:
+            raise RuntimeError("FusedAdamW.accumulate: first=False with nothing accumulated")
+        elif self._pending[0] != sig:
+            raise RuntimeError("FusedAdamW.accumulate: the parameters with gradients changed between micro-batches")
+        for spans in work:
+            for arena, o, n, _ in spans:
+                ops.grad_accum(self._accumulator(arena)[o:o + n], arena.grad[o:o + n], w, first)
+        for group in self.param_groups:
+            for p in group["params"]:
+                p.grad = None
+
+    def reduce_accumulated(self):
+        """Data parallelism: SUM all-reduce of the pending accumulators, once per optimizer step
+        (one collective per span), for modules whose backward was told not to reduce each
+        micro-batch.  Every micro-batch must have been folded by accumulate()."""
+        from . import dist as vdist
+        if self._pending is None:
+            raise RuntimeError("FusedAdamW.reduce_accumulated: nothing accumulated")
+        for spans in self._pending[1]:
+            for arena, o, n, _ in spans:
+                vdist.all_reduce_sum_(self._accumulator(arena)[o:o + n])
+
+    @torch.no_grad()
+    def step(self, closure=None, w=1.0):
+        """`w`: the weight of the fresh gradients when micro-batches are pending (acc + w * g)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         # every group's spans first: the norm covers all of them before any update
         self._copied = []
-        work = [(group, self._spans(group)) for group in self.param_groups]
+        spans_of = [self._spans(group) for group in self.param_groups]
+        self._src = None
+        if self._pending is not None:
+            sig, folded = self._pending
+            self._pending = None
+            if not self._signature(spans_of):
+                spans_of, self._src = folded, ("acc",)     # every micro-batch was folded
+            elif self._signature(spans_of) == sig:
+                self._src = ("sum", float(w))
+                self._copied = []                            # neither kernel writes g back
+            else:
+                raise RuntimeError("FusedAdamW.step: the parameters with gradients differ from the accumulated ones")
+        work = list(zip(self.param_groups, spans_of))
         if self._clip is not None and self._clip[0] == "norm":
             self._launch_norm([s for _, spans in work for s in spans])
         for group, spans in work:
@@ -160,6 +236,7 @@ class FusedAdamW(torch.optim.Optimizer):
         for grad, g in self._copied:   # p.grad outside the arena: leave it clipped as well
             grad.copy_(g)
         self._copied = []
+        self._src = None
         return loss
 
     def _launch_norm(self, spans):
@@ -171,16 +248,27 @@ class FusedAdamW(torch.optim.Optimizer):
         partials, out = self._clip_buffers(spans[0][0].grad.device, total)
         off = 0
         for arena, o, n, _ in spans:
-            off += ops.grad_sumsq(arena.grad[o:o + n], partials, off)
+            if self._src is None:
+                off += ops.grad_sumsq(arena.grad[o:o + n], partials, off)
+            elif self._src[0] == "acc":
+                off += ops.grad_sumsq(self._accumulator(arena)[o:o + n], partials, off)
+            else:
+                off += ops.grad_accum_sumsq(self._accumulator(arena)[o:o + n], arena.grad[o:o + n], self._src[1],
+                                            partials, off)
         ops.clip_coef(off, partials, self._clip[1], out)
         self.last_grad_norm = out[0]
 
     def _launch(self, arena, o, n, group, step):
         b1, b2 = group["betas"]
         m, v = self._moments(arena)
-        args = (arena.data[o:o + n], arena.grad[o:o + n], m[o:o + n], v[o:o + n],
+        grad = self._accumulator(arena) if self._src == ("acc",) else arena.grad
+        args = (arena.data[o:o + n], grad[o:o + n], m[o:o + n], v[o:o + n],
                 group["lr"], b1, b2, group["eps"], group["weight_decay"], step)
-        if self._clip is None:
+        if self._src is not None and self._src[0] == "sum":
+            kw = {} if self._clip is None else (dict(coef=self._clip_bufs[1][1:]) if self._clip[0] == "norm"
+                                                else dict(clip_value=self._clip[1]))
+            ops.adamw_clip_accum(*args, acc=self._accumulator(arena)[o:o + n], w=self._src[1], **kw)
+        elif self._clip is None:
             ops.adamw(*args)
         elif self._clip[0] == "norm":
             ops.adamw_clip(*args, coef=self._clip_bufs[1][1:])
@@ -204,6 +292,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     self._bind(p)
 
     def zero_grad(self, set_to_none: bool = True):
+        self._pending = None   # accumulated micro-batches are gradients too
         for group in self.param_groups:
             for p in group["params"]:
                 p.grad = None
