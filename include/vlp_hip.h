@@ -575,6 +575,28 @@ int vlp_adamw_clip_accum(long long n, float* p, float* g, float* m, float* v, fl
                          float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
                          const float* coef, float clip_value, const float* acc, float w,
                          void* stream);
+/* Replace torch.optim.Adam (configs/optimizer/adam.yaml:3, the `optimizer: adam` experiments;
+ * built by the reference's configure_optimizers, VisionLanguageModule.py:130-184, from the same
+ * parameter groups) with clipping and accumulation fused as above.  Adam differs from AdamW in
+ * the weight decay alone: it is an L2 term of the gradient, not a decay of the parameter.
+ * Arguments as vlp_adamw_clip_accum; per element
+ *   s  = acc ? fmaf(w, g[i], acc[i]) : g[i]
+ *   c  = mode 1: s * coef[0] (coef a DEVICE pointer) | mode 2: clamp(s, +-clip_value) | mode 0: s
+ *   gd = fmaf(wd, p[i], c)           (torch: grad + weight_decay * param, after the clipping)
+ *   m, v, p: vlp_adamw's moment and parameter update on gd, without its p *= 1 - lr * wd
+ * (lr enters through step_size alone).  With wd == 0 the results are the bits of vlp_adamw
+ * (acc == NULL, mode 0), vlp_adamw_clip (acc == NULL, modes 1 / 2) or vlp_adamw_clip_accum.
+ * All six combinations of mode 0..2 with and without acc are valid.  With acc, g and acc are left
+ * alone; without, modes 1 / 2 store c back to g (what torch leaves in p.grad: the clipped
+ * gradient, never gd) and mode 0 only reads g.  One pass over 4 or 5 fp32 streams in and 3 or 4
+ * out, the bytes vlp_adamw_clip_accum moves for the same case.  Same conventions: no host
+ * synchronisation, no atomics, bitwise reproducible; 16-B vector accesses where the operands share
+ * their 16-B misalignment, scalar ones otherwise; every pointer needs 4-B alignment.
+ * hipErrorInvalidValue with nothing launched: a NULL or misaligned p / g / m / v with n > 0, a
+ * misaligned acc, a NULL coef in mode 1, a mode outside 0..2.  n <= 0 launches nothing, returns 0. */
+int vlp_adam_step(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                  float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                  const float* coef, float clip_value, const float* acc, float w, void* stream);
 int vlp_pack_conv(int dtype, int Co, int C, int KH, int KW, const float* w, void* wp, void* wt,
                   void* stream);
 /* vlp_pack_conv for n <= 48 convolutions in one launch: desc holds n rows of

@@ -5,6 +5,8 @@
 //   p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // over flat fp32 parameter / gradient / state arenas (one launch per group).
+// Adam (torch.optim.Adam, configs/optimizer/adam.yaml) shares the moment and parameter update
+// and differs in the weight decay alone: g += wd p in front of the moments, no p *= 1 - lr*wd.
 //
 // Packing turns the fp32 master conv weights (timm [Co][C][KH][KW]) into the
 // GEMM operand layouts of conv_ops.hip, and the weight-gradient workspaces back.
@@ -14,18 +16,38 @@
 
 namespace vlp {
 
+// The moment and parameter update of every step kernel below (AdamW and Adam alike): gi is the
+// gradient the moments see, decay the factor on the parameter (AdamW: 1 - lr*wd, Adam: 1).
+// 1 - beta is formed in fp32.  Returns the new parameter; m and v are updated in place.
+// Every rounding is spelled out (no contraction in here).  FUSE: v * b2 + sq and p * decay - u
+// are one fused multiply-add each, else a product and a sum; the 16-B vector body of the
+// accumulating kernels is FUSE, every scalar access path is not.  That is the arithmetic each
+// kernel has had since it was written: its results do not change with the code around it.
+template <bool FUSE>
+__device__ __forceinline__ float adam_update(float p, float decay, float gi, float& m, float& v, float b1, float b2,
+                                             float eps, float step_size, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  float mi = fmaf(1.f - b1, gi - m, m);   // torch exp_avg.lerp_(grad, 1-beta1)
+  float sq = (1.f - b2) * gi * gi;
+  float vi = FUSE ? fmaf(b2, v, sq) : v * b2 + sq;
+  m = mi;
+  v = vi;
+  float denom = sqrtf(vi) / bc2_sqrt + eps;
+  float q = mi / denom;
+  return FUSE ? fmaf(decay, p, -step_size * q) : p * decay - step_size * q;
+}
+
 __global__ void adamw_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v, float lr, float b1,
                              float b2, float eps, float wd, float step_size, float bc2_sqrt) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float pi = p[i] * (1.f - lr * wd);
+    float pi = p[i];
     float gi = g[i];
-    float mi = fmaf(1.f - b1, gi - m[i], m[i]);   // torch exp_avg.lerp_(grad, 1-beta1)
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    pi = adam_update<false>(pi, 1.f - lr * wd, gi, mi, vi, b1, b2, eps, step_size, bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
+    p[i] = pi;
   }
 }
 
@@ -104,7 +126,7 @@ __global__ void adamw_clip_kernel(size_t n, float* __restrict__ p, float* __rest
                                   const float* __restrict__ coef, float clip_value) {
   const float c = MODE == 1 ? coef[0] : 0.f;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float pi = p[i] * (1.f - lr * wd);
+    float pi = p[i];
     float gi = g[i];
     if (MODE == 1) {
       gi = gi * c;
@@ -115,12 +137,11 @@ __global__ void adamw_clip_kernel(size_t n, float* __restrict__ p, float* __rest
       gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
     }
     g[i] = gi;
-    float mi = fmaf(1.f - b1, gi - m[i], m[i]);   // torch exp_avg.lerp_(grad, 1-beta1)
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    pi = adam_update<false>(pi, 1.f - lr * wd, gi, mi, vi, b1, b2, eps, step_size, bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
+    p[i] = pi;
   }
 }
 
@@ -199,11 +220,10 @@ __global__ void __launch_bounds__(256) grad_accum_sumsq_kernel(size_t n, const f
 }
 
 // MODE 0: no clipping, 1: * coef[0], 2: clamp(+-clip_value), as adamw_clip_kernel
-template <int MODE>
+template <int MODE, bool FUSE>
 __device__ __forceinline__ void adamw_accum_update(float& p, float g, float a, float& m, float& v, float w, float lr,
                                                    float b1, float b2, float eps, float wd, float step_size,
                                                    float bc2_sqrt, float c, float clip_value) {
-  float pi = p * (1.f - lr * wd);
   float gi = fmaf(w, g, a);
   // the accumulated gradient is an fp32 value of its own (torch's p.grad after the last
   // backward), as is the clipped one: the empty asm keeps each from being contracted further
@@ -214,12 +234,7 @@ __device__ __forceinline__ void adamw_accum_update(float& p, float g, float a, f
   } else if (MODE == 2) {
     gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
   }
-  float mi = fmaf(1.f - b1, gi - m, m);   // torch exp_avg.lerp_(grad, 1-beta1)
-  float vi = v * b2 + (1.f - b2) * gi * gi;
-  m = mi;
-  v = vi;
-  float denom = sqrtf(vi) / bc2_sqrt + eps;
-  p = pi - step_size * (mi / denom);
+  p = adam_update<FUSE>(p, 1.f - lr * wd, gi, m, v, b1, b2, eps, step_size, bc2_sqrt);
 }
 
 template <int MODE>
@@ -240,10 +255,10 @@ __global__ void __launch_bounds__(256) adamw_accum_kernel(size_t n, float* __res
   for (size_t i = tid; i < nvec; i += nthr) {
     float4 pp = p4[i], mm = m4[i], vv = v4[i];
     const float4 gg = g4[i], aa = a4[i];
-    adamw_accum_update<MODE>(pp.x, gg.x, aa.x, mm.x, vv.x, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE>(pp.y, gg.y, aa.y, mm.y, vv.y, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE>(pp.z, gg.z, aa.z, mm.z, vv.z, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE>(pp.w, gg.w, aa.w, mm.w, vv.w, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE, true>(pp.x, gg.x, aa.x, mm.x, vv.x, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE, true>(pp.y, gg.y, aa.y, mm.y, vv.y, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE, true>(pp.z, gg.z, aa.z, mm.z, vv.z, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
+    adamw_accum_update<MODE, true>(pp.w, gg.w, aa.w, mm.w, vv.w, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
     m4[i] = mm;
     v4[i] = vv;
     p4[i] = pp;
@@ -251,8 +266,82 @@ __global__ void __launch_bounds__(256) adamw_accum_kernel(size_t n, float* __res
   const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
   for (size_t j = tid; j < nsc; j += nthr) {
     const size_t i = j < head ? j : tail0 + (j - head);
-    adamw_accum_update<MODE>(p[i], g[i], acc[i], m[i], v[i], w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c,
+    adamw_accum_update<MODE, false>(p[i], g[i], acc[i], m[i], v[i], w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c,
                              clip_value);
+  }
+}
+
+// torch.optim.Adam (configs/optimizer/adam.yaml): the same step with the weight decay as an L2
+// term of the gradient, gd = c + wd p in front of the moments, and no decay of the parameter.
+// c is the gradient after accumulation and clipping, as in the AdamW kernels above: clipping
+// acts on the gradient alone, so c (what torch leaves in p.grad), never gd, is what goes back
+// to g.  One kernel for every case: ACC reads fmaf(w, g, acc) and writes neither g nor acc;
+// without ACC, modes 1 / 2 store c to g and mode 0 only reads it.  wd == 0: gd = c, and with
+// adam_update's FUSE chosen as the AdamW twin of each case has it (the accumulating kernel's
+// vector body) the results are the AdamW kernels' bits.
+template <int MODE, bool ACC, bool FUSE>
+__device__ __forceinline__ void adam_step_update(float& p, float& g, float a, float& m, float& v, float w, float b1,
+                                                 float b2, float eps, float wd, float step_size, float bc2_sqrt,
+                                                 float c, float clip_value, float one) {
+  float gi = g;
+  if (ACC) {
+    gi = fmaf(w, gi, a);
+    asm("" : "+v"(gi));   // an fp32 value of its own, as in adamw_accum_update
+  }
+  if (MODE == 1) {
+    gi = gi * c;
+    asm("" : "+v"(gi));
+  } else if (MODE == 2) {
+    gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
+  }
+  if (!ACC && MODE != 0) g = gi;
+  const float gd = fmaf(wd, p, gi);   // torch grad.add(param, alpha=weight_decay)
+  p = adam_update<FUSE>(p, one, gd, m, v, b1, b2, eps, step_size, bc2_sqrt);
+}
+
+template <int MODE, bool ACC>
+__global__ void __launch_bounds__(256) adam_step_kernel(size_t n, float* __restrict__ p, float* __restrict__ g,
+                                                        const float* __restrict__ acc, float* __restrict__ m,
+                                                        float* __restrict__ v, float w, float b1, float b2, float eps,
+                                                        float wd, float step_size, float bc2_sqrt,
+                                                        const float* __restrict__ coef, float clip_value, size_t head) {
+  constexpr bool kStoreG = !ACC && MODE != 0;
+  // the parameter's factor, 1, kept from the compiler: a literal would fold fma(1, p, -u) into an add
+  // and then fuse u's product into it, one rounding where AdamW with wd == 0 has two
+  float one = 1.f;
+  asm("" : "+v"(one));
+  const float c = MODE == 1 ? coef[0] : 0.f;
+  const size_t nvec = (n - head) >> 2;
+  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
+  float4* p4 = reinterpret_cast<float4*>(p + head);
+  float4* m4 = reinterpret_cast<float4*>(m + head);
+  float4* v4 = reinterpret_cast<float4*>(v + head);
+  float4* g4 = reinterpret_cast<float4*>(g + head);
+  const float4* a4 = ACC ? reinterpret_cast<const float4*>(acc + head) : nullptr;
+  for (size_t i = tid; i < nvec; i += nthr) {
+    float4 pp = p4[i], mm = m4[i], vv = v4[i], gg = g4[i];
+    float4 aa = {0.f, 0.f, 0.f, 0.f};
+    if (ACC) aa = a4[i];
+    adam_step_update<MODE, ACC, ACC>(pp.x, gg.x, aa.x, mm.x, vv.x, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
+                                     one);
+    adam_step_update<MODE, ACC, ACC>(pp.y, gg.y, aa.y, mm.y, vv.y, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
+                                     one);
+    adam_step_update<MODE, ACC, ACC>(pp.z, gg.z, aa.z, mm.z, vv.z, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
+                                     one);
+    adam_step_update<MODE, ACC, ACC>(pp.w, gg.w, aa.w, mm.w, vv.w, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
+                                     one);
+    if (kStoreG) g4[i] = gg;
+    m4[i] = mm;
+    v4[i] = vv;
+    p4[i] = pp;
+  }
+  const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
+  for (size_t j = tid; j < nsc; j += nthr) {
+    const size_t i = j < head ? j : tail0 + (j - head);
+    float gi = g[i];
+    adam_step_update<MODE, ACC, false>(p[i], gi, ACC ? acc[i] : 0.f, m[i], v[i], w, b1, b2, eps, wd, step_size, bc2_sqrt, c,
+                                clip_value, one);
+    if (kStoreG) g[i] = gi;
   }
 }
 
@@ -529,6 +618,42 @@ VLP_EXPORT int vlp_adamw_clip_accum(long long n, float* p, float* g, float* m, f
   else
     VLP_ACCUM_LAUNCH(2);
 #undef VLP_ACCUM_LAUNCH
+  return (int)hipGetLastError();
+}
+
+// torch.optim.Adam's step (L2 weight decay) on acc + w g (acc != NULL; g and acc left alone) or on g
+// (acc == NULL; modes 1 / 2 store the clipped gradient back to g), clipped as vlp_adamw_clip_accum
+// clips.  All of mode 0..2 with and without acc are valid.
+VLP_EXPORT int vlp_adam_step(long long n, float* p, float* g, float* m, float* v, float lr, float beta1, float beta2,
+                             float eps, float wd, float step_size, float bc2_sqrt, int mode, const float* coef,
+                             float clip_value, const float* acc, float w, void* stream) {
+  (void)lr;   // Adam has no lr * wd term: lr enters through step_size alone
+  if (mode < 0 || mode > 2 || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) & 3) return (int)hipErrorInvalidValue;
+  const size_t head = acc ? common_head((size_t)n, {p, g, m, v, acc}) : common_head((size_t)n, {p, g, m, v});
+  const dim3 grid(vec_grid_for(n)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define VLP_ADAM_LAUNCH(MODE, ACC)                                                                                  \
+  hipLaunchKernelGGL((adam_step_kernel<MODE, ACC>), grid, block, 0, st, (size_t)n, p, g, acc, m, v, w, beta1, beta2, \
+                     eps, wd, step_size, bc2_sqrt, coef, clip_value, head)
+  if (acc) {
+    if (mode == 0)
+      VLP_ADAM_LAUNCH(0, true);
+    else if (mode == 1)
+      VLP_ADAM_LAUNCH(1, true);
+    else
+      VLP_ADAM_LAUNCH(2, true);
+  } else {
+    if (mode == 0)
+      VLP_ADAM_LAUNCH(0, false);
+    else if (mode == 1)
+      VLP_ADAM_LAUNCH(1, false);
+    else
+      VLP_ADAM_LAUNCH(2, false);
+  }
+#undef VLP_ADAM_LAUNCH
   return (int)hipGetLastError();
 }
 

@@ -13,8 +13,10 @@ Additions (keyword-only, defaults keep reference behaviour where possible):
   compute_dtype  "fp32" (the reference's arithmetic, default) | "bf16" (throughput mode,
                  the _mi355x experiments; src/train.py also derives it from trainer.precision)
   text_dropout   text tower hidden/attention dropout (reference: 0.1 from the hub configs)
-  fused_optimizer  build vlp_amd.FusedAdamW when the configured optimizer is
-                   torch.optim.AdamW (same hyper-parameters / param groups)
+  fused_optimizer  build vlp_amd.optim.FusedAdamW when the configured optimizer is
+                   torch.optim.AdamW, vlp_amd.optim.FusedAdam when it is torch.optim.Adam
+                   (same hyper-parameters / param groups; clipping and accumulation fused on
+                   the device).  Adam with amsgrad or maximize stays torch.optim.Adam
   device         where the parameter arenas live (default: cuda)
   duplicate_caption_mask  (in **kwargs, default False) leave duplicate-caption negatives
                  out of the contrastive loss: under data parallelism the global batch
@@ -42,7 +44,7 @@ if _PKG not in sys.path:
 from vlp_amd import ops  # noqa: E402
 from vlp_amd.clip_model import (ClipHead, ClipStepFn, _project_normalize, caption_hash64,  # noqa: E402
                                 compact_caption_ids, role_weights)
-from vlp_amd.optim import FusedAdamW  # noqa: E402
+from vlp_amd.optim import FusedAdam, FusedAdamW  # noqa: E402
 from vlp_amd.nest import NEST_CFGS, NestTower  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
 from vlp_amd.vit import VIT_CFGS, ViTTower  # noqa: E402
@@ -386,10 +388,17 @@ class VisionLanguageModule(_Base):
         param_groups = self._configure_optimizer_parameters()
         opt_factory = self.hparams.optimizer
         func = getattr(opt_factory, "func", opt_factory)
+        kw = dict(getattr(opt_factory, "keywords", {}) or {})
+        fused_adam = self.hparams.get("fused_optimizer", True) and func is torch.optim.Adam
+        if fused_adam and (kw.get("amsgrad") or kw.get("maximize")):
+            logger.info("torch.optim.Adam with amsgrad / maximize has no fused step: keeping torch's optimizer")
+            fused_adam = False
         if self.hparams.get("fused_optimizer", True) and func is torch.optim.AdamW:
-            kw = dict(getattr(opt_factory, "keywords", {}) or {})
             optimizer = FusedAdamW(param_groups, arenas=[self._head, self.image_encoder.model,
                                                          self.text_encoder.model], **kw)
+        elif fused_adam:
+            optimizer = FusedAdam(param_groups, arenas=[self._head, self.image_encoder.model,
+                                                        self.text_encoder.model], **kw)
         else:
             optimizer = opt_factory(params=param_groups)
         for group in optimizer.param_groups:

@@ -690,6 +690,22 @@ def adamw_clip_accum(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc, w=1.0, co
                                mode, ptr(coef), float(clip_value or 0.0), ptr(acc), float(w), _s())
 
 
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc=None, w=1.0, coef=None, clip_value=None):
+    """torch.optim.Adam's step (weight decay as an L2 term of the gradient, added after the
+    clipping) on acc + w * g, or on g alone (acc=None), scaled by coef[0] (device fp32, norm
+    clipping), clamped to +-clip_value, or as it is (neither given).  With acc, g and acc are
+    not written; without, the clipped gradient is written back to g."""
+    if coef is not None and clip_value is not None:
+        raise ValueError("adam_step: at most one of coef / clip_value")
+    _f32_flat("adam_step", p, g, m, v, *(() if acc is None else (acc,)))
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    mode = 1 if coef is not None else 2 if clip_value is not None else 0
+    lib().vlp_adam_step(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
+                        float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
+                        mode, ptr(coef), float(clip_value or 0.0), ptr(acc), float(w), _s())
+
+
 def pack_conv(w, wp, wt):
     Co, C, KH, KW = w.shape
     ref = wp if wp is not None else wt

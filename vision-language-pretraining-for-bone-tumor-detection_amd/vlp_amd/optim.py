@@ -1,7 +1,9 @@
-"""Fused AdamW over flat parameter arenas (replaces torch.optim.AdamW, the
+"""Fused AdamW and Adam over flat parameter arenas.  FusedAdamW replaces torch.optim.AdamW (the
 reference's optimizer: configs/optimizer/adamw.yaml, built in
 VisionLanguageModule.configure_optimizers :130-184 from the parameter groups of
-_configure_optimizer_parameters :186-243).
+_configure_optimizer_parameters :186-243); FusedAdam, at the end of this file, is the same
+machinery for torch.optim.Adam (configs/optimizer/adam.yaml), whose step differs in the weight
+decay alone.
 
 Same parameter-group semantics as torch.optim.AdamW: per-group lr, parameters
 whose .grad is None are skipped entirely (the unused TinyBERT pooler, as in the
@@ -296,3 +298,48 @@ class FusedAdamW(torch.optim.Optimizer):
         for group in self.param_groups:
             for p in group["params"]:
                 p.grad = None
+
+
+class FusedAdam(FusedAdamW):
+    """torch.optim.Adam (configs/optimizer/adam.yaml, the reference's `optimizer: adam`
+    experiments) over the same arenas: FusedAdamW with the weight decay as an L2 term of the
+    gradient (torch's grad.add(param, alpha=weight_decay), after any clipping) in place of the
+    decay of the parameter, and torch.optim.Adam's defaults (weight_decay 0).  Every case of the
+    step -- plain, clipped by norm or value, on fresh gradients, on acc + w*g or on the
+    accumulator alone -- is one `vlp_adam_step` launch per span; spans, step counts, the norm
+    pass, accumulate(), reduce_accumulated(), zero_grad() and the moment buffers are
+    FusedAdamW's.  The clipped gradient that is written back to g is the one torch leaves in
+    p.grad: without the L2 term.
+
+    The parameter groups carry torch.optim.Adam's remaining keys at their defaults, so a
+    state_dict() loads into torch.optim.Adam and one of torch's loads here.  amsgrad and
+    maximize have no kernel and raise ValueError."""
+
+    _TORCH_KEYS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
+                       fused=None)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
+                 maximize=False, arenas=None):
+        if amsgrad or maximize:
+            raise ValueError("FusedAdam: amsgrad / maximize are not implemented on the device (use torch.optim.Adam)")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, arenas=arenas)
+        for k, v in self._TORCH_KEYS.items():
+            self.defaults.setdefault(k, v)
+            for group in self.param_groups:
+                group.setdefault(k, v)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        if any(g.get("amsgrad") or g.get("maximize") for g in self.param_groups):
+            raise ValueError("FusedAdam: the loaded state asks for amsgrad / maximize")
+
+    def _launch(self, arena, o, n, group, step):
+        b1, b2 = group["betas"]
+        m, v = self._moments(arena)
+        grad = self._accumulator(arena) if self._src == ("acc",) else arena.grad
+        kw = {} if self._clip is None else (dict(coef=self._clip_bufs[1][1:]) if self._clip[0] == "norm"
+                                            else dict(clip_value=self._clip[1]))
+        if self._src is not None and self._src[0] == "sum":
+            kw.update(acc=self._accumulator(arena)[o:o + n], w=self._src[1])
+        ops.adam_step(arena.data[o:o + n], grad[o:o + n], m[o:o + n], v[o:o + n],
+                      group["lr"], b1, b2, group["eps"], group["weight_decay"], step, **kw)
