@@ -398,6 +398,20 @@ int vlp_scatter_rows(int dtype, int R, int D, const void* in, int ldi, void* out
  * (fp32 vlp_linear_fwd of normalised embeddings). */
 int vlp_row_topk(int R, int N, const float* x, long long ldx, int K, float* vals, int* idx, void* stream);
 
+/* ---------------- post-fit silhouette scores ----------------
+ * Replace sklearn's silhouette_score over the best checkpoint's cached features in
+ * plot_tsne_and_calculate_silhouette.py:56-60 (called from train.py:179-183 and :261-327):
+ * sums[q][c] (fp32, [Q][C] dense) = sum over keys j with key_label[j] == c of
+ * ||xq[q] - xk[j]||_2, each distance sqrtf(sum_d (a_d - b_d)^2) from direct fp32 differences
+ * (a row against itself or a duplicate is exactly 0).  One launch for all of Q, nothing of
+ * size Q x N is stored, no atomics: two calls agree bit for bit and equal query rows give
+ * equal bits.  A key whose label is outside [0, C) adds to no column (callers validate the
+ * labels); Q == 0 returns 0 with no launch, N == 0 writes zeros.  hipErrorInvalidValue before
+ * any launch: C < 1, C > 8, D < 1, ldq < D, ldk < D, a negative Q or N, Q or N within 128 of
+ * INT_MAX, a NULL xq or sums, a NULL xk or key_label with N > 0. */
+int vlp_cluster_dist_sums(int Q, int N, int D, const float* xq, long long ldq, const float* xk,
+                          long long ldk, const int* key_label, int C, float* sums, void* stream);
+
 /* ---------------- NesT image encoder (BASELINE configs[3]) ----------------
  * Replace timm nest.py's pieces behind ImageEncoder's timm.create_model("nest_small", ...)
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,

@@ -39,7 +39,8 @@ _PKG = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "..", "..")
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
-from src.models.pretrain.VisionLanguageModule import _Base, _HAVE_LIGHTNING, _default_device  # noqa: E402
+from src.models.pretrain.VisionLanguageModule import (VisionLanguageModule, _Base, _HAVE_LIGHTNING,  # noqa: E402
+                                                       _default_device)
 from src.utils.coral_loss.coral import coral  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
 
@@ -152,6 +153,10 @@ class FusionModule(_Base):
 
     def get_image_network(self):
         return self.image_network
+
+    # Lightning-format checkpoint -> module (weights_only=True), as VisionLanguageModule's;
+    # the post-fit evaluation reloads the best checkpoint with it (train.py:305)
+    load_from_checkpoint = classmethod(VisionLanguageModule.load_from_checkpoint.__func__)
 
     # ---------------- optimizer (:127-201) ----------------
     def configure_optimizers(self):

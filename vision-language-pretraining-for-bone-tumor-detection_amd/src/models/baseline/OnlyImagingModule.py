@@ -47,7 +47,8 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from src.models.baseline.FusionModule import FusionModule, ResNet34Classifier  # noqa: E402
-from src.models.pretrain.VisionLanguageModule import _Base, _HAVE_LIGHTNING, _default_device  # noqa: E402
+from src.models.pretrain.VisionLanguageModule import (VisionLanguageModule, _Base, _HAVE_LIGHTNING,  # noqa: E402
+                                                       _default_device)
 from vlp_amd.nest import NestTower  # noqa: E402
 
 logger = logging.getLogger("project")
@@ -193,6 +194,9 @@ class OnlyImagingModule(_Base):
 
     def get_image_network(self):
         return self.network
+
+    # Lightning-format checkpoint -> module, as VisionLanguageModule's (the post-fit evaluation, train.py:305)
+    load_from_checkpoint = classmethod(VisionLanguageModule.load_from_checkpoint.__func__)
 
     def all_reduce_gradients(self, world: int) -> None:
         """Data-parallel gradient mean (the trainer's DDP hook): the tower's flat

@@ -15,9 +15,17 @@ Same entry points and flow for the VLP pretraining experiments:
               aggregated over folds (:231-262).
 The late-fusion finetune (FusionModule + DownstreamDataModule) runs through the
 same path: `experiment=baseline_imaging_and_clinical/baseline_imaging_and_clinical_resnet_34`.
+The imaging-only baseline (OnlyImagingModule, the default model of configs/train.yaml)
+runs through it as well.  For either baseline module the reference ends a run with an
+evaluation of the best checkpoint (:179-183, :261-327): silhouette scores of the image
+features by tumour label and by source dataset and the confusion matrix, for the
+validation and train loaders.  The reference gates it on a W&B logger; here the
+top-level key `post_fit_evaluation: true` turns it on (absent = off), e.g.
+`experiment=baseline_only_imaging/baseline_only_imaging_resnet_34_mi355x_eval`, and the
+numbers join the fold's metrics (src/utils/post_fit_evaluation.py).
 Out of scope: W&B loggers (configured loggers whose package is
-absent are skipped with a warning), t-SNE / confusion-matrix plots, downstream
-zero-shot evaluation and the OnlyImaging baseline module.
+absent are skipped with a warning), the t-SNE and confusion-matrix figures and
+downstream zero-shot evaluation.
 
 Multi-GPU: launch one process per GPU (`python -m torch.distributed.run
 --nproc-per-node N src/train.py ...`); train() initialises torch.distributed
@@ -171,6 +179,9 @@ def train(cfg: Dict[str, Any]) -> Tuple[Dict[str, Any], Dict[str, Any]]:
             if getattr(model, "downstream_datamodule", None) is not None:
                 for k, v in model.evaluate_downstream_precision_at_k(mode="entire").items():
                     fold_metrics[f"downstream_entire/label_precision_at_{k}"] = v
+        elif cfg.get("post_fit_evaluation", False) and "VisionLanguageModule" not in model_cfg["_target_"]:
+            from src.utils.post_fit_evaluation import post_fit_evaluation   # :179-183
+            fold_metrics.update(post_fit_evaluation(model, fold_dm, trainer))
         all_fold_metrics.append(fold_metrics)
         if not cfg.get("k_fold_cross_validation", False):
             break

@@ -1,0 +1,118 @@
+"""Post-fit evaluation of the baseline modules' best checkpoint (reference
+src/train.py:179-183 and :261-327, plot_tsne_and_calculate_silhouette.py:15-98,
+plot_confusion_matrix.py:14-60): two silhouette scores of the image network's
+features (clusters = tumour label, clusters = source dataset) and the 2x2
+confusion matrix at a 0.5 threshold, for the validation and the train loaders.
+
+Only the numbers are computed: the t-SNE and the figures need W&B and are not
+built.  Each batch goes through the module once (features and logits come from
+the same forward); the features stay on the device and the silhouette's distance
+sums run there (vlp_amd/metrics.py -> vlp_cluster_dist_sums), only the tumour
+labels and dataset names are host lists.  There are no collectives: under data
+parallelism every rank evaluates the loaders it is given.
+"""
+from __future__ import annotations
+
+import logging
+import os
+from typing import Any, Dict
+
+import torch
+
+from vlp_amd import metrics
+
+log = logging.getLogger("project")
+
+
+def best_checkpoint_callback(trainer):
+    """The checkpoint callback whose best model is evaluated (train.py:283-296): the
+    first one monitoring a `combined` metric, else the last one monitoring a `btxrd`
+    metric, else None."""
+    callbacks = getattr(trainer, "checkpoint_callbacks", None)
+    if callbacks is None:
+        callbacks = [cb for cb in getattr(trainer, "callbacks", []) if hasattr(cb, "best_model_path")]
+    btxrd = combined = None
+    for cb in callbacks:
+        monitor = getattr(cb, "monitor", None) or ""
+        if "btxrd" in monitor:
+            btxrd = cb
+        if "combined" in monitor:
+            combined = cb
+            break
+    return combined if combined is not None else btxrd
+
+
+def _features_and_logits(model, batch):
+    """One pass: (features [B, F] or [B, F, h, w], logits [B])."""
+    from src.models.baseline.FusionModule import FusionModule
+    if isinstance(model, FusionModule):
+        x, _, _, site, age, sex = model._unpack(batch)
+        logits, features = model(x, age, sex, site)
+        return features, logits
+    x = model._unpack(batch)[0]
+    features = model.forward_features(x)
+    return features, model.forward_head(features)
+
+
+def evaluate_split(model, dataloaders) -> Dict[str, Any]:
+    """Silhouette scores and confusion matrix of `model` over a loader or a list of loaders."""
+    if not isinstance(dataloaders, (list, tuple)):
+        dataloaders = [dataloaders]
+    was_training = model.training
+    model.eval()
+    feats, preds, tumor, dataset = [], [], [], []
+    try:
+        with torch.no_grad():
+            for loader in dataloaders:
+                for batch in loader:
+                    f, logits = _features_and_logits(model, batch)
+                    if f.dim() == 4:
+                        f = f.mean((2, 3))
+                    feats.append(f.float())
+                    preds.append(torch.sigmoid(logits.float().flatten()) > 0.5)   # strict, plot_confusion_matrix.py:48
+                    tumor.extend(int(t) for t in batch["tumor"].tolist())
+                    dataset.extend(batch["dataset"])
+    finally:
+        model.train(was_training)
+    x, pred = torch.cat(feats), torch.cat(preds)
+    y = torch.tensor(tumor, dtype=torch.bool, device=pred.device)
+    tn, fp = int((~pred & ~y).sum()), int((pred & ~y).sum())
+    fn, tp = int((~pred & y).sum()), int((pred & y).sum())
+    if len(set(dataset)) < 2:
+        log.warning("post_fit_evaluation: the split holds one dataset name only (%s); its dataset silhouette "
+                    "score is nan", sorted(set(dataset)))
+        by_dataset = float("nan")
+    else:
+        by_dataset = metrics.silhouette_score(x, dataset)
+    return {"silhouette_score_based_on_tumor": metrics.silhouette_score(x, tumor),
+            "silhouette_score_based_on_dataset": by_dataset,
+            "confusion_matrix": [[tn, fp], [fn, tp]]}
+
+
+def post_fit_evaluation(model, datamodule, trainer) -> Dict[str, Any]:
+    """Reload the best checkpoint and evaluate the validation and train loaders; the
+    reference's W&B keys, the confusion matrix as four counts per split."""
+    cb = best_checkpoint_callback(trainer)
+    if cb is None:
+        log.info("Train: No silhouette scores or confusion matrix, since no checkpoint callback monitoring a "
+                 "combined or btxrd metric was found.")
+        return {}
+    path = cb.best_model_path
+    if not path or not os.path.exists(path):
+        log.warning("Train: the checkpoint callback monitoring %s saved no best model; no post-fit evaluation.",
+                    cb.monitor)
+        return {}
+    log.info("Train: Calculating silhouette scores and confusion matrix of validation and train data with the "
+             "best %s model: %s", cb.monitor, path)
+    best = type(model).load_from_checkpoint(path, device=model.device)
+    out: Dict[str, Any] = {}
+    for split, loaders in (("validation", datamodule.val_dataloader()), ("train", datamodule.train_dataloader())):
+        res = evaluate_split(best, loaders)
+        out[f"silhouette_score_based_on_tumor_{split}"] = res["silhouette_score_based_on_tumor"]
+        out[f"silhouette_score_based_on_dataset_{split}"] = res["silhouette_score_based_on_dataset"]
+        (tn, fp), (fn, tp) = res["confusion_matrix"]
+        for k, v in (("tn", tn), ("fp", fp), ("fn", fn), ("tp", tp)):
+            out[f"confusion_matrix_{split}/{k}"] = v
+    for k, v in out.items():
+        log.info("Train: %s = %s", k, v)
+    return out

@@ -773,6 +773,34 @@ def sim_topk(q, keys, K):
     return vals, idx.long()
 
 
+# ---------------- post-fit silhouette scores ----------------
+MAX_CLUSTERS = 8   # kMaxClusters of csrc/retrieval_ops.hip
+
+
+def cluster_dist_sums(x, labels_i32, C, xq=None):
+    """[Q, C] fp32: out[q, c] = sum over rows j of x with labels_i32[j] == c of
+    ||xq[q] - x[j]||_2 (xq defaults to x), every distance from direct fp32
+    differences (vlp_cluster_dist_sums: one launch, no Q x N matrix, bitwise
+    reproducible).  x [N, D], xq [Q, D]; C <= 8 and every label in [0, C), else
+    ValueError -- the label range is read back once, the only host sync here."""
+    C = int(C)
+    if not 1 <= C <= MAX_CLUSTERS:
+        raise ValueError(f"cluster_dist_sums: C={C}, the kernel keeps 1 to {MAX_CLUSTERS} clusters")
+    x = x.float().contiguous()
+    xq = x if xq is None else xq.float().contiguous()
+    labels_i32 = labels_i32.to(device=x.device, dtype=torch.int32).contiguous()
+    N, D = x.shape
+    Q = xq.shape[0]
+    if xq.dim() != 2 or xq.shape[1] != D or labels_i32.shape != (N,):
+        raise ValueError(f"cluster_dist_sums: x {tuple(x.shape)}, xq {tuple(xq.shape)}, "
+                         f"labels {tuple(labels_i32.shape)} do not fit")
+    if N and not (0 <= int(labels_i32.min()) and int(labels_i32.max()) < C):
+        raise ValueError(f"cluster_dist_sums: labels must lie in [0, {C})")
+    out = torch.empty(Q, C, dtype=torch.float32, device=x.device)
+    lib().vlp_cluster_dist_sums(Q, N, D, ptr(xq), D, ptr(x), D, ptr(labels_i32), C, ptr(out), _s())
+    return out
+
+
 # ---------------- NesT image encoder (SURVEY §8(f) row 2) ----------------
 def nest_attn_fwd(qkv, out, lse, BT, H, N, scale):
     tk = ktimer.begin("nest_attn_fwd", 4.0 * BT * H * N * N * 32)
