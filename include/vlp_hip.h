@@ -537,7 +537,12 @@ int vlp_cast(int dtype, long long n, const float* x, void* y, void* stream);
 
 /* ---------------- optimizer / packing ----------------
  * Replace torch.optim.AdamW as built by configure_optimizers
- * (VisionLanguageModule.py:130-184, configs/optimizer/adamw.yaml:1-3). */
+ * (VisionLanguageModule.py:130-184, configs/optimizer/adamw.yaml:1-3).
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) come from the host.  g is only
+ * read.  vlp_adamw and the three step entry points below are one kernel and one set of checks:
+ * 16-B vector accesses where p, g, m, v (and acc) share their 16-B misalignment, scalar ones
+ * otherwise; a NULL or not 4-B aligned p / g / m / v with n > 0 is hipErrorInvalidValue with
+ * nothing launched; n <= 0 launches nothing and returns 0. */
 int vlp_adamw(long long n, float* p, const float* g, float* m, float* v, float lr, float beta1,
               float beta2, float eps, float wd, float step_size, float bc2_sqrt, void* stream);
 /* Gradient clipping on the device: replace torch.nn.utils.clip_grad_norm_ / clip_grad_value_
@@ -550,7 +555,7 @@ int vlp_adamw(long long n, float* p, const float* g, float* m, float* v, float l
  * span, elements [16384 s, 16384 (s + 1)); *nparts (host memory, written during the call) =
  * ceil(n / 16384), a function of n alone, so several spans can be laid end to end in one
  * partials buffer.  g needs only 4-B alignment.  n <= 0: *nparts = 0, nothing launched, returns 0;
- * a NULL pointer: hipErrorInvalidValue, nothing launched.
+ * a NULL pointer or a g that is not 4-B aligned: hipErrorInvalidValue, nothing launched.
  * vlp_grad_sumsq_nparts: the same count without a launch (to size the partials buffer). */
 int vlp_grad_sumsq_nparts(long long n, int* nparts);
 int vlp_grad_sumsq(long long n, const float* g, double* partials, int* nparts, void* stream);

@@ -1153,7 +1153,7 @@ def adamw_emulate(d):
 @pytest.mark.parametrize("step", (1, 2, 1000))
 @pytest.mark.parametrize("n", ADAM_N)
 def test_adamw(ops, n, step, wd):
-    """adamw_kernel against the fp64 formula, and the formula against torch.optim.AdamW in fp64 on the
+    """vlp_adamw against the fp64 formula, and the formula against torch.optim.AdamW in fp64 on the
     CPU (n <= 257; test 1 covers it without a device as well)."""
     dev = "cuda"
     d = adamw_inputs(n, step, wd, 100 + step)
@@ -1182,6 +1182,26 @@ def test_adamw_n0_is_a_noop(ops):
     ops.adamw(bufs[0][:0], bufs[1][:0], bufs[2][:0], bufs[3][:0], 5e-5, 0.9, 0.999, 1e-8, 0.01, 1)
     torch.cuda.synchronize()
     assert all(bool((b == SENT).all().item()) for b in bufs)
+
+
+@gpu
+def test_adamw_rejects_null_and_misaligned_operands(ops):
+    """vlp_adamw checks its operands as the other step entry points do: a NULL or not 4-B aligned
+    pointer with n > 0 is hipErrorInvalidValue (1) and nothing is launched."""
+    from vlp_amd._lib import lib, stream_of
+    raw = lib()._fns["vlp_adamw"]
+    t = [torch.ones(4, device="cuda") for _ in range(4)]
+    ptrs = [x.data_ptr() for x in t]
+    tail = (1e-3, 0.9, 0.999, 1e-8, 0.01, 1e-2, 0.03, stream_of())
+    for i in range(4):
+        for bad in (None, ptrs[i] + 2):
+            q = list(ptrs)
+            q[i] = bad
+            assert raw(4, *q, *tail) == 1, (i, bad)
+    for n in (0, -5):
+        assert raw(n, None, None, None, None, *tail) == 0
+    torch.cuda.synchronize()
+    assert all(bool((x == 1).all().item()) for x in t)
 
 
 # ---------------------------------------------------------------- CPU: the bounds are satisfiable

@@ -17,7 +17,7 @@ Bounds.
   update: where torch and the kernel evaluate the same fp32 expression the results may differ
     by the order of one or two roundings: <= 2 ulp.
 
-Hyper-parameters of the "vs torch" moment checks: adamw_kernel forms 1 - beta in fp32
+Hyper-parameters of the "vs torch" moment checks: the step kernel forms 1 - beta in fp32
 (1.f - 0.999f = 0.99998712e-3) where torch rounds the double 1 - 0.999 to fp32 (1.0000000475e-3):
 1.3e-5 apart with the default betas (the known envelope of tests/test_gpu_bn_routes.py
 test_adamw), which would drown the <= 2 ulp / 1e-6 checks of what the clip adds.  Those checks

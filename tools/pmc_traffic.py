@@ -48,7 +48,7 @@ def main():
            "method": "rocprofv3 --pmc FETCH_SIZE (x2 gfx950 correction, KiB->B) and a separate "
                      "--pmc WRITE_SIZE pass (KiB->B), averaged over the matching dispatches"}
     # calibration: the AdamW kernel streams 16 B/element in and 12 B/element out
-    cal = [k for k in fe if "adamw_kernel" in k]
+    cal = [k for k in fe if "step_kernel<false, 0, false>" in k]
     if cal:
         res["calibration_adamw"] = {"fetch_bytes_mean": 2048.0 * sum(fe[cal[0]]) / len(fe[cal[0]]),
                                     "write_bytes_mean": 1024.0 * sum(wr.get(cal[0], [0])) / max(len(wr.get(cal[0], [])), 1)}

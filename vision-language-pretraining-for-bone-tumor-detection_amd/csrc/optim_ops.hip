@@ -7,6 +7,9 @@
 // over flat fp32 parameter / gradient / state arenas (one launch per group).
 // Adam (torch.optim.Adam, configs/optimizer/adam.yaml) shares the moment and parameter update
 // and differs in the weight decay alone: g += wd p in front of the moments, no p *= 1 - lr*wd.
+// Both, with and without gradient clipping and a gradient accumulator, are one kernel template,
+// step_kernel<L2, MODE, ACC>; the gradient norm, with and without the accumulator, is
+// sumsq_kernel<ACC>.
 //
 // Packing turns the fp32 master conv weights (timm [Co][C][KH][KW]) into the
 // GEMM operand layouts of conv_ops.hip, and the weight-gradient workspaces back.
@@ -16,13 +19,13 @@
 
 namespace vlp {
 
-// The moment and parameter update of every step kernel below (AdamW and Adam alike): gi is the
-// gradient the moments see, decay the factor on the parameter (AdamW: 1 - lr*wd, Adam: 1).
+// The moment and parameter update of every step (AdamW and Adam alike): gi is the gradient the
+// moments see, decay the factor on the parameter (AdamW: 1 - lr*wd, Adam: 1).
 // 1 - beta is formed in fp32.  Returns the new parameter; m and v are updated in place.
 // Every rounding is spelled out (no contraction in here).  FUSE: v * b2 + sq and p * decay - u
-// are one fused multiply-add each, else a product and a sum; the 16-B vector body of the
-// accumulating kernels is FUSE, every scalar access path is not.  That is the arithmetic each
-// kernel has had since it was written: its results do not change with the code around it.
+// are one fused multiply-add each, else a product and a sum; step_kernel's 16-B vector body is
+// FUSE when it reads an accumulator, every other access path is not.  That is the arithmetic each
+// case has had since it was written (tests/test_gpu_optim_bits.py holds every bit of it).
 template <bool FUSE>
 __device__ __forceinline__ float adam_update(float p, float decay, float gi, float& m, float& v, float b1, float b2,
                                              float eps, float step_size, float bc2_sqrt) {
@@ -37,29 +40,21 @@ __device__ __forceinline__ float adam_update(float p, float decay, float gi, flo
   return FUSE ? fmaf(decay, p, -step_size * q) : p * decay - step_size * q;
 }
 
-__global__ void adamw_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g,
-                             float* __restrict__ m, float* __restrict__ v, float lr, float b1,
-                             float b2, float eps, float wd, float step_size, float bc2_sqrt) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    float gi = g[i];
-    float mi = m[i], vi = v[i];
-    pi = adam_update<false>(pi, 1.f - lr * wd, gi, mi, vi, b1, b2, eps, step_size, bc2_sqrt);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-
 // Gradient clipping (torch.nn.utils.clip_grad_norm_ / clip_grad_value_, Lightning's
 // gradient_clip_val) on the device, with no host read-back and no atomics:
-//   grad_sumsq_kernel  fp64 sum of g^2 per fixed-length segment of a span -> partials
-//   clip_coef_kernel   one workgroup: norm = sqrt(sum of all partials), coef = min(1, max / (norm + 1e-6))
-//   adamw_clip_kernel  adamw_kernel on gi = g * coef (MODE 1) or clamp(g, +-clip_value) (MODE 2),
-//                      gi written back to g
+//   sumsq_kernel      fp64 sum of s^2 per fixed-length segment of a span -> partials, with s the
+//                     gradient g or (ACC) the accumulated one, fmaf(w, g, acc)
+//   clip_coef_kernel  one workgroup: norm = sqrt(sum of all partials), coef = min(1, max / (norm + 1e-6))
+//   step_kernel       the step on s * coef (MODE 1) or clamp(s, +-clip_value) (MODE 2)
 // A span's segment s is its elements [s * kSumsqSeg, (s + 1) * kSumsqSeg): the partials are a
 // function of the span alone, not of the grid or the CU count, and every sum below has a fixed
 // order, so a rerun reproduces the norm bit for bit.
+//
+// Spans start anywhere in an arena: `head` elements in front of the first 16-B boundary are
+// scalar, then 16-B vectors, then a scalar tail.  Operands that do not share their 16-B
+// misalignment (never the case for spans of equally laid out arenas) take head = n: all scalar.
+__host__ __device__ __forceinline__ int vec_head(const void* a) { return (int)(((16 - ((uintptr_t)a & 15)) & 15) >> 2); }
+
 constexpr int kSumsqSeg = 16384;   // elements per partial (a multiple of 4: every segment of a span
                                    // has the span's 16-B misalignment)
 
@@ -75,31 +70,42 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
 
 __device__ __forceinline__ double sq_f64(float x) { return (double)x * (double)x; }   // exact
 
-__global__ void __launch_bounds__(256) grad_sumsq_kernel(size_t n, const float* __restrict__ g,
-                                                         double* __restrict__ partials, int nparts) {
+// ACC: s = fmaf(w, g, acc), else s = g (acc is not read).  vec = 0: scalar loads only.  In each
+// segment the head goes to a0, the vectors' lanes to a0..a3 and the tail to a1.
+template <bool ACC>
+__global__ void __launch_bounds__(256) sumsq_kernel(size_t n, const float* __restrict__ acc,
+                                                    const float* __restrict__ g, float w,
+                                                    double* __restrict__ partials, int nparts, int vec) {
   __shared__ double red[4];
   const int tid = threadIdx.x;
-  // elements in front of the first 16-B boundary (spans start anywhere in an arena)
-  const int mis = (int)(((16 - ((uintptr_t)g & 15)) & 15) >> 2);
+  const int mis = vec_head(g);
   for (int s = blockIdx.x; s < nparts; s += gridDim.x) {
-    const float* seg = g + (size_t)s * kSumsqSeg;
-    const size_t left = n - (size_t)s * kSumsqSeg;
+    const size_t base = (size_t)s * kSumsqSeg;
+    const float* gs = g + base;
+    const float* as = acc + base;
+    const size_t left = n - base;
     const int len = left < (size_t)kSumsqSeg ? (int)left : kSumsqSeg;
-    const int head = mis < len ? mis : len;
+    const int head = vec ? (mis < len ? mis : len) : len;
     const int nvec = (len - head) >> 2;
     const int tail0 = head + 4 * nvec;
+    auto sq = [&](int i) { return sq_f64(ACC ? fmaf(w, gs[i], as[i]) : gs[i]); };
     double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
-    if (tid < head) a0 = sq_f64(seg[tid]);
-    const float4* body = reinterpret_cast<const float4*>(seg + head);
+    for (int i = tid; i < head; i += 256) a0 += sq(i);
+    const float4* gb = reinterpret_cast<const float4*>(gs + head);
+    const float4* ab = reinterpret_cast<const float4*>(as + head);
 #pragma unroll 4
     for (int i = tid; i < nvec; i += 256) {
-      const float4 q = body[i];
+      float4 q = gb[i];
+      if (ACC) {
+        const float4 a = ab[i];
+        q.x = fmaf(w, q.x, a.x); q.y = fmaf(w, q.y, a.y); q.z = fmaf(w, q.z, a.z); q.w = fmaf(w, q.w, a.w);
+      }
       a0 += sq_f64(q.x);
       a1 += sq_f64(q.y);
       a2 += sq_f64(q.z);
       a3 += sq_f64(q.w);
     }
-    if (tail0 + tid < len) a1 += sq_f64(seg[tail0 + tid]);
+    if (tail0 + tid < len) a1 += sq(tail0 + tid);
     const double t = block_sum_f64((a0 + a1) + (a2 + a3), red);
     if (tid == 0) partials[s] = t;
   }
@@ -119,45 +125,15 @@ __global__ void __launch_bounds__(256) clip_coef_kernel(int nparts, const double
   }
 }
 
-template <int MODE>
-__global__ void adamw_clip_kernel(size_t n, float* __restrict__ p, float* __restrict__ g,
-                                  float* __restrict__ m, float* __restrict__ v, float lr, float b1,
-                                  float b2, float eps, float wd, float step_size, float bc2_sqrt,
-                                  const float* __restrict__ coef, float clip_value) {
-  const float c = MODE == 1 ? coef[0] : 0.f;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    float pi = p[i];
-    float gi = g[i];
-    if (MODE == 1) {
-      gi = gi * c;
-      // torch rounds the clipped gradient to fp32 before AdamW reads it: the empty asm
-      // keeps the product from being contracted into the multiply-adds below
-      asm("" : "+v"(gi));
-    } else {
-      gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
-    }
-    g[i] = gi;
-    float mi = m[i], vi = v[i];
-    pi = adam_update<false>(pi, 1.f - lr * wd, gi, mi, vi, b1, b2, eps, step_size, bc2_sqrt);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-
 // Gradient accumulation (Lightning's accumulate_grad_batches) over the flat arenas.  The
 // backward overwrites the gradient arena, so every micro-batch but the last of an optimizer
 // step is folded into an accumulator of the same layout, and the last one is folded in by
 // the step itself:
-//   grad_accum_kernel        acc = (FIRST ? 0 : acc) + w g            one pass, 3 (FIRST: 2) streams
-//   grad_accum_sumsq_kernel  grad_sumsq_kernel on fmaf(w, g, acc)     the accumulated gradient's norm
-//   adamw_accum_kernel       adamw_clip_kernel on fmaf(w, g, acc)     nothing written back to g / acc
+//   grad_accum_kernel  acc = (FIRST ? 0 : acc) + w g              one pass, 3 (FIRST: 2) streams
+//   sumsq_kernel<ACC>  the norm of fmaf(w, g, acc)                the accumulated gradient's norm
+//   step_kernel<ACC>   the step on fmaf(w, g, acc)                nothing written back to g / acc
 // fmaf(w, g, acc) is one rounding; the norm kernel and the step form it with the same
 // instruction from the same operands, so the norm is that of the gradient the step uses.
-// Spans start anywhere in an arena: `head` elements in front of the first 16-B boundary are
-// scalar, then 16-B vectors, then a scalar tail.  Operands that do not share their 16-B
-// misalignment (never the case for spans of equally laid out arenas) take head = n: all scalar.
-__host__ __device__ __forceinline__ int vec_head(const void* a) { return (int)(((16 - ((uintptr_t)a & 15)) & 15) >> 2); }
 
 template <bool FIRST>
 __global__ void __launch_bounds__(256) grad_accum_kernel(size_t n, float* __restrict__ acc,
@@ -185,131 +161,53 @@ __global__ void __launch_bounds__(256) grad_accum_kernel(size_t n, float* __rest
   }
 }
 
-// grad_sumsq_kernel's segments and reduction order on s = fmaf(w, g, acc); vec = 0: scalar loads
-__global__ void __launch_bounds__(256) grad_accum_sumsq_kernel(size_t n, const float* __restrict__ acc,
-                                                               const float* __restrict__ g, float w,
-                                                               double* __restrict__ partials, int nparts, int vec) {
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
-  const int mis = vec_head(g);
-  for (int s = blockIdx.x; s < nparts; s += gridDim.x) {
-    const size_t base = (size_t)s * kSumsqSeg;
-    const float* gs = g + base;
-    const float* as = acc + base;
-    const size_t left = n - base;
-    const int len = left < (size_t)kSumsqSeg ? (int)left : kSumsqSeg;
-    const int head = vec ? (mis < len ? mis : len) : len;
-    const int nvec = (len - head) >> 2;
-    const int tail0 = head + 4 * nvec;
-    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
-    for (int i = tid; i < head; i += 256) a0 += sq_f64(fmaf(w, gs[i], as[i]));
-    const float4* gb = reinterpret_cast<const float4*>(gs + head);
-    const float4* ab = reinterpret_cast<const float4*>(as + head);
-#pragma unroll 4
-    for (int i = tid; i < nvec; i += 256) {
-      const float4 q = gb[i], a = ab[i];
-      a0 += sq_f64(fmaf(w, q.x, a.x));
-      a1 += sq_f64(fmaf(w, q.y, a.y));
-      a2 += sq_f64(fmaf(w, q.z, a.z));
-      a3 += sq_f64(fmaf(w, q.w, a.w));
-    }
-    if (tail0 + tid < len) a1 += sq_f64(fmaf(w, gs[tail0 + tid], as[tail0 + tid]));
-    const double t = block_sum_f64((a0 + a1) + (a2 + a3), red);
-    if (tid == 0) partials[s] = t;
-  }
-}
+// The optimizer step, every case of it.
+//   gradient      ACC: s = fmaf(w, g, acc), else s = g
+//                 MODE 0: c = s;  1: c = s * coef[0];  2: c = clamp(s, +-clip_value)
+//                 c (what torch leaves in p.grad) goes back to g when it differs from what g
+//                 holds, !ACC && MODE != 0; acc is never written
+//   weight decay  L2 (torch.optim.Adam): gd = c + wd p in front of the moments, the parameter's
+//                 factor is 1;  else (AdamW): gd = c, the factor is 1 - lr wd
+// With wd == 0 the two are the same step, bit for bit: fmaf(0, p, c) is c and the factor is 1.
+struct StepArgs {
+  float w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, clip_value;
+};
 
-// MODE 0: no clipping, 1: * coef[0], 2: clamp(+-clip_value), as adamw_clip_kernel
-template <int MODE, bool FUSE>
-__device__ __forceinline__ void adamw_accum_update(float& p, float g, float a, float& m, float& v, float w, float lr,
-                                                   float b1, float b2, float eps, float wd, float step_size,
-                                                   float bc2_sqrt, float c, float clip_value) {
-  float gi = fmaf(w, g, a);
-  // the accumulated gradient is an fp32 value of its own (torch's p.grad after the last
-  // backward), as is the clipped one: the empty asm keeps each from being contracted further
-  asm("" : "+v"(gi));
-  if (MODE == 1) {
-    gi = gi * c;
-    asm("" : "+v"(gi));
-  } else if (MODE == 2) {
-    gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
-  }
-  p = adam_update<FUSE>(p, 1.f - lr * wd, gi, m, v, b1, b2, eps, step_size, bc2_sqrt);
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) adamw_accum_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g,
-                                                          const float* __restrict__ acc, float* __restrict__ m,
-                                                          float* __restrict__ v, float w, float lr, float b1, float b2,
-                                                          float eps, float wd, float step_size, float bc2_sqrt,
-                                                          const float* __restrict__ coef, float clip_value,
-                                                          size_t head) {
-  const float c = MODE == 1 ? coef[0] : 0.f;
-  const size_t nvec = (n - head) >> 2;
-  const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
-  float4* p4 = reinterpret_cast<float4*>(p + head);
-  float4* m4 = reinterpret_cast<float4*>(m + head);
-  float4* v4 = reinterpret_cast<float4*>(v + head);
-  const float4* g4 = reinterpret_cast<const float4*>(g + head);
-  const float4* a4 = reinterpret_cast<const float4*>(acc + head);
-  for (size_t i = tid; i < nvec; i += nthr) {
-    float4 pp = p4[i], mm = m4[i], vv = v4[i];
-    const float4 gg = g4[i], aa = a4[i];
-    adamw_accum_update<MODE, true>(pp.x, gg.x, aa.x, mm.x, vv.x, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE, true>(pp.y, gg.y, aa.y, mm.y, vv.y, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE, true>(pp.z, gg.z, aa.z, mm.z, vv.z, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    adamw_accum_update<MODE, true>(pp.w, gg.w, aa.w, mm.w, vv.w, w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value);
-    m4[i] = mm;
-    v4[i] = vv;
-    p4[i] = pp;
-  }
-  const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
-  for (size_t j = tid; j < nsc; j += nthr) {
-    const size_t i = j < head ? j : tail0 + (j - head);
-    adamw_accum_update<MODE, false>(p[i], g[i], acc[i], m[i], v[i], w, lr, b1, b2, eps, wd, step_size, bc2_sqrt, c,
-                             clip_value);
-  }
-}
-
-// torch.optim.Adam (configs/optimizer/adam.yaml): the same step with the weight decay as an L2
-// term of the gradient, gd = c + wd p in front of the moments, and no decay of the parameter.
-// c is the gradient after accumulation and clipping, as in the AdamW kernels above: clipping
-// acts on the gradient alone, so c (what torch leaves in p.grad), never gd, is what goes back
-// to g.  One kernel for every case: ACC reads fmaf(w, g, acc) and writes neither g nor acc;
-// without ACC, modes 1 / 2 store c to g and mode 0 only reads it.  wd == 0: gd = c, and with
-// adam_update's FUSE chosen as the AdamW twin of each case has it (the accumulating kernel's
-// vector body) the results are the AdamW kernels' bits.
-template <int MODE, bool ACC, bool FUSE>
-__device__ __forceinline__ void adam_step_update(float& p, float& g, float a, float& m, float& v, float w, float b1,
-                                                 float b2, float eps, float wd, float step_size, float bc2_sqrt,
-                                                 float c, float clip_value, float one) {
+// one element; coef is coef[0] (MODE 1), decay the parameter's factor
+template <bool L2, int MODE, bool ACC, bool FUSE>
+__device__ __forceinline__ void step_update(float& p, float& g, float a, float& m, float& v, const StepArgs& s,
+                                            float coef, float decay) {
   float gi = g;
   if (ACC) {
-    gi = fmaf(w, gi, a);
-    asm("" : "+v"(gi));   // an fp32 value of its own, as in adamw_accum_update
+    gi = fmaf(s.w, gi, a);
+    // the accumulated gradient is an fp32 value of its own (torch's p.grad after the last
+    // backward), as is the clipped one: the empty asm keeps each from being contracted further
+    asm("" : "+v"(gi));
   }
   if (MODE == 1) {
-    gi = gi * c;
+    gi = gi * coef;
     asm("" : "+v"(gi));
   } else if (MODE == 2) {
-    gi = gi < -clip_value ? -clip_value : (gi > clip_value ? clip_value : gi);   // NaN stays, as torch.clamp
+    gi = gi < -s.clip_value ? -s.clip_value : (gi > s.clip_value ? s.clip_value : gi);   // NaN stays, as torch.clamp
   }
   if (!ACC && MODE != 0) g = gi;
-  const float gd = fmaf(wd, p, gi);   // torch grad.add(param, alpha=weight_decay)
-  p = adam_update<FUSE>(p, one, gd, m, v, b1, b2, eps, step_size, bc2_sqrt);
+  const float gd = L2 ? fmaf(s.wd, p, gi) : gi;   // torch grad.add(param, alpha=weight_decay)
+  p = adam_update<FUSE>(p, decay, gd, m, v, s.b1, s.b2, s.eps, s.step_size, s.bc2_sqrt);
 }
 
-template <int MODE, bool ACC>
-__global__ void __launch_bounds__(256) adam_step_kernel(size_t n, float* __restrict__ p, float* __restrict__ g,
-                                                        const float* __restrict__ acc, float* __restrict__ m,
-                                                        float* __restrict__ v, float w, float b1, float b2, float eps,
-                                                        float wd, float step_size, float bc2_sqrt,
-                                                        const float* __restrict__ coef, float clip_value, size_t head) {
+template <bool L2, int MODE, bool ACC>
+__global__ void __launch_bounds__(256) step_kernel(size_t n, float* __restrict__ p, float* __restrict__ g,
+                                                   const float* __restrict__ acc, float* __restrict__ m,
+                                                   float* __restrict__ v, StepArgs s, const float* __restrict__ coef,
+                                                   size_t head) {
   constexpr bool kStoreG = !ACC && MODE != 0;
-  // the parameter's factor, 1, kept from the compiler: a literal would fold fma(1, p, -u) into an add
+  // Adam's factor, 1, kept from the compiler: a literal would fold fma(1, p, -u) into an add
   // and then fuse u's product into it, one rounding where AdamW with wd == 0 has two
-  float one = 1.f;
-  asm("" : "+v"(one));
+  float decay = 1.f;
+  if (L2)
+    asm("" : "+v"(decay));
+  else
+    decay = 1.f - s.lr * s.wd;
   const float c = MODE == 1 ? coef[0] : 0.f;
   const size_t nvec = (n - head) >> 2;
   const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x, nthr = (size_t)gridDim.x * blockDim.x;
@@ -322,25 +220,21 @@ __global__ void __launch_bounds__(256) adam_step_kernel(size_t n, float* __restr
     float4 pp = p4[i], mm = m4[i], vv = v4[i], gg = g4[i];
     float4 aa = {0.f, 0.f, 0.f, 0.f};
     if (ACC) aa = a4[i];
-    adam_step_update<MODE, ACC, ACC>(pp.x, gg.x, aa.x, mm.x, vv.x, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
-                                     one);
-    adam_step_update<MODE, ACC, ACC>(pp.y, gg.y, aa.y, mm.y, vv.y, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
-                                     one);
-    adam_step_update<MODE, ACC, ACC>(pp.z, gg.z, aa.z, mm.z, vv.z, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
-                                     one);
-    adam_step_update<MODE, ACC, ACC>(pp.w, gg.w, aa.w, mm.w, vv.w, w, b1, b2, eps, wd, step_size, bc2_sqrt, c, clip_value,
-                                     one);
+    step_update<L2, MODE, ACC, ACC>(pp.x, gg.x, aa.x, mm.x, vv.x, s, c, decay);
+    step_update<L2, MODE, ACC, ACC>(pp.y, gg.y, aa.y, mm.y, vv.y, s, c, decay);
+    step_update<L2, MODE, ACC, ACC>(pp.z, gg.z, aa.z, mm.z, vv.z, s, c, decay);
+    step_update<L2, MODE, ACC, ACC>(pp.w, gg.w, aa.w, mm.w, vv.w, s, c, decay);
     if (kStoreG) g4[i] = gg;
     m4[i] = mm;
     v4[i] = vv;
     p4[i] = pp;
   }
+  // the head and what follows the vectors (at most 3 + 3 elements unless all scalar)
   const size_t tail0 = head + 4 * nvec, nsc = head + (n - tail0);
   for (size_t j = tid; j < nsc; j += nthr) {
     const size_t i = j < head ? j : tail0 + (j - head);
     float gi = g[i];
-    adam_step_update<MODE, ACC, false>(p[i], gi, ACC ? acc[i] : 0.f, m[i], v[i], w, b1, b2, eps, wd, step_size, bc2_sqrt, c,
-                                clip_value, one);
+    step_update<L2, MODE, ACC, false>(p[i], gi, ACC ? acc[i] : 0.f, m[i], v[i], s, c, decay);
     if (kStoreG) g[i] = gi;
   }
 }
@@ -499,16 +393,6 @@ static inline int grid_for(size_t n) {
 
 using namespace vlp;
 
-// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), computed in fp64 on the host
-VLP_EXPORT int vlp_adamw(long long n, float* p, const float* g, float* m, float* v, float lr,
-                         float beta1, float beta2, float eps, float wd, float step_size,
-                         float bc2_sqrt, void* stream) {
-  if (n <= 0) return 0;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n, p, g,
-                     m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt);
-  return (int)hipGetLastError();
-}
-
 // partials of an n-element span: a function of n alone (host side, no GPU work)
 VLP_EXPORT int vlp_grad_sumsq_nparts(long long n, int* nparts) {
   if (!nparts || n > (long long)kSumsqSeg * 0x7fffffffll) return (int)hipErrorInvalidValue;
@@ -516,38 +400,10 @@ VLP_EXPORT int vlp_grad_sumsq_nparts(long long n, int* nparts) {
   return 0;
 }
 
-VLP_EXPORT int vlp_grad_sumsq(long long n, const float* g, double* partials, int* nparts, void* stream) {
-  int np = 0;
-  if (int e = vlp_grad_sumsq_nparts(n, &np)) return e;
-  if (nparts) *nparts = np;
-  if (n <= 0) return 0;
-  if (!g || !partials || !nparts) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(np < 2048 ? np : 2048), dim3(256), 0, (hipStream_t)stream,
-                     (size_t)n, g, partials, np);
-  return (int)hipGetLastError();
-}
-
 VLP_EXPORT int vlp_clip_coef(int nparts, const double* partials, float max_norm, float* out, void* stream) {
   if (nparts < 0 || !out || (nparts > 0 && !partials)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nparts, partials,
                      max_norm, out);
-  return (int)hipGetLastError();
-}
-
-// vlp_adamw on the clipped gradient, which is also written back to g.
-// mode 1: g * coef[0] (coef on the device: vlp_clip_coef's out + 1); mode 2: clamp(g, +-clip_value)
-VLP_EXPORT int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
-                              float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
-                              const float* coef, float clip_value, void* stream) {
-  if ((mode != 1 && mode != 2) || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
-  if (n <= 0) return 0;
-  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
-  if (mode == 1)
-    hipLaunchKernelGGL(adamw_clip_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
-                       p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value);
-  else
-    hipLaunchKernelGGL(adamw_clip_kernel<2>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (size_t)n,
-                       p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value);
   return (int)hipGetLastError();
 }
 
@@ -581,16 +437,69 @@ VLP_EXPORT int vlp_grad_accum(long long n, float* acc, const float* g, float w, 
   return (int)hipGetLastError();
 }
 
-VLP_EXPORT int vlp_grad_accum_sumsq(long long n, const float* acc, const float* g, float w, double* partials,
-                                    int* nparts, void* stream) {
+// vlp_grad_sumsq (ACC false: acc is not looked at) and vlp_grad_accum_sumsq
+template <bool ACC>
+static int launch_sumsq(long long n, const float* acc, const float* g, float w, double* partials, int* nparts,
+                        void* stream) {
   int np = 0;
   if (int e = vlp_grad_sumsq_nparts(n, &np)) return e;
   if (nparts) *nparts = np;
   if (n <= 0) return 0;
+  if (!ACC) acc = g;
   if (!acc || !g || !partials || !nparts || (((uintptr_t)acc | (uintptr_t)g) & 3)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(grad_accum_sumsq_kernel, dim3(np < 2048 ? np : 2048), dim3(256), 0, (hipStream_t)stream,
-                     (size_t)n, acc, g, w, partials, np, vec_head(acc) == vec_head(g) ? 1 : 0);
+  hipLaunchKernelGGL(sumsq_kernel<ACC>, dim3(np < 2048 ? np : 2048), dim3(256), 0, (hipStream_t)stream, (size_t)n, acc,
+                     g, w, partials, np, vec_head(acc) == vec_head(g) ? 1 : 0);
   return (int)hipGetLastError();
+}
+
+VLP_EXPORT int vlp_grad_sumsq(long long n, const float* g, double* partials, int* nparts, void* stream) {
+  return launch_sumsq<false>(n, nullptr, g, 0.f, partials, nparts, stream);
+}
+
+VLP_EXPORT int vlp_grad_accum_sumsq(long long n, const float* acc, const float* g, float w, double* partials,
+                                    int* nparts, void* stream) {
+  return launch_sumsq<true>(n, acc, g, w, partials, nparts, stream);
+}
+
+// Every step entry point ends here: step_kernel<l2, mode, acc != NULL> over n elements, after the
+// checks they share.  A bad mode is an error whatever n is; n <= 0 is a no-op whatever the pointers are.
+using StepKernel = void (*)(size_t, float*, float*, const float*, float*, float*, StepArgs, const float*, size_t);
+static const StepKernel kStepKernels[2][3][2] = {
+    {{step_kernel<false, 0, false>, step_kernel<false, 0, true>},
+     {step_kernel<false, 1, false>, step_kernel<false, 1, true>},
+     {step_kernel<false, 2, false>, step_kernel<false, 2, true>}},
+    {{step_kernel<true, 0, false>, step_kernel<true, 0, true>},
+     {step_kernel<true, 1, false>, step_kernel<true, 1, true>},
+     {step_kernel<true, 2, false>, step_kernel<true, 2, true>}}};
+
+static int launch_step(bool l2, long long n, float* p, float* g, float* m, float* v, const StepArgs& s, int mode,
+                       const float* coef, const float* acc, void* stream) {
+  if (mode < 0 || mode > 2 || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
+  if (n <= 0) return 0;
+  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) & 3) return (int)hipErrorInvalidValue;
+  const size_t head = acc ? common_head((size_t)n, {p, g, m, v, acc}) : common_head((size_t)n, {p, g, m, v});
+  hipLaunchKernelGGL(kStepKernels[l2][mode][acc != nullptr], dim3(vec_grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                     (size_t)n, p, g, acc, m, v, s, coef, head);
+  return (int)hipGetLastError();
+}
+
+// step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), computed in fp64 on the host
+VLP_EXPORT int vlp_adamw(long long n, float* p, const float* g, float* m, float* v, float lr,
+                         float beta1, float beta2, float eps, float wd, float step_size,
+                         float bc2_sqrt, void* stream) {
+  const StepArgs s{0.f, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, 0.f};
+  return launch_step(false, n, p, const_cast<float*>(g), m, v, s, 0, nullptr, nullptr, stream);   // mode 0 only reads g
+}
+
+// vlp_adamw on the clipped gradient, which is also written back to g.
+// mode 1: g * coef[0] (coef on the device: vlp_clip_coef's out + 1); mode 2: clamp(g, +-clip_value)
+VLP_EXPORT int vlp_adamw_clip(long long n, float* p, float* g, float* m, float* v, float lr, float beta1,
+                              float beta2, float eps, float wd, float step_size, float bc2_sqrt, int mode,
+                              const float* coef, float clip_value, void* stream) {
+  if (mode == 0) return (int)hipErrorInvalidValue;   // vlp_adamw's job
+  const StepArgs s{0.f, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, clip_value};
+  return launch_step(false, n, p, g, m, v, s, mode, coef, nullptr, stream);
 }
 
 // vlp_adamw_clip on coef * (acc + w g) (mode 1), clamp(acc + w g) (mode 2) or acc + w g itself
@@ -601,60 +510,19 @@ VLP_EXPORT int vlp_adamw_clip_accum(long long n, float* p, float* g, float* m, f
   if (!acc)
     return vlp_adamw_clip(n, p, g, m, v, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, mode, coef, clip_value,
                           stream);
-  if (mode < 0 || mode > 2 || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
-  if (n <= 0) return 0;
-  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) & 3) return (int)hipErrorInvalidValue;
-  const size_t head = common_head((size_t)n, {p, g, m, v, acc});
-  const dim3 grid(vec_grid_for(n)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define VLP_ACCUM_LAUNCH(MODE)                                                                                   \
-  hipLaunchKernelGGL(adamw_accum_kernel<MODE>, grid, block, 0, st, (size_t)n, p, (const float*)g, acc, m, v, w, lr, \
-                     beta1, beta2, eps, wd, step_size, bc2_sqrt, coef, clip_value, head)
-  if (mode == 0)
-    VLP_ACCUM_LAUNCH(0);
-  else if (mode == 1)
-    VLP_ACCUM_LAUNCH(1);
-  else
-    VLP_ACCUM_LAUNCH(2);
-#undef VLP_ACCUM_LAUNCH
-  return (int)hipGetLastError();
+  const StepArgs s{w, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, clip_value};
+  return launch_step(false, n, p, g, m, v, s, mode, coef, acc, stream);
 }
 
 // torch.optim.Adam's step (L2 weight decay) on acc + w g (acc != NULL; g and acc left alone) or on g
 // (acc == NULL; modes 1 / 2 store the clipped gradient back to g), clipped as vlp_adamw_clip_accum
-// clips.  All of mode 0..2 with and without acc are valid.
+// clips.  All of mode 0..2 with and without acc are valid.  Adam has no lr * wd term: lr enters
+// through step_size alone.
 VLP_EXPORT int vlp_adam_step(long long n, float* p, float* g, float* m, float* v, float lr, float beta1, float beta2,
                              float eps, float wd, float step_size, float bc2_sqrt, int mode, const float* coef,
                              float clip_value, const float* acc, float w, void* stream) {
-  (void)lr;   // Adam has no lr * wd term: lr enters through step_size alone
-  if (mode < 0 || mode > 2 || (mode == 1 && !coef)) return (int)hipErrorInvalidValue;
-  if (n <= 0) return 0;
-  if (!p || !g || !m || !v) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)acc) & 3) return (int)hipErrorInvalidValue;
-  const size_t head = acc ? common_head((size_t)n, {p, g, m, v, acc}) : common_head((size_t)n, {p, g, m, v});
-  const dim3 grid(vec_grid_for(n)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define VLP_ADAM_LAUNCH(MODE, ACC)                                                                                  \
-  hipLaunchKernelGGL((adam_step_kernel<MODE, ACC>), grid, block, 0, st, (size_t)n, p, g, acc, m, v, w, beta1, beta2, \
-                     eps, wd, step_size, bc2_sqrt, coef, clip_value, head)
-  if (acc) {
-    if (mode == 0)
-      VLP_ADAM_LAUNCH(0, true);
-    else if (mode == 1)
-      VLP_ADAM_LAUNCH(1, true);
-    else
-      VLP_ADAM_LAUNCH(2, true);
-  } else {
-    if (mode == 0)
-      VLP_ADAM_LAUNCH(0, false);
-    else if (mode == 1)
-      VLP_ADAM_LAUNCH(1, false);
-    else
-      VLP_ADAM_LAUNCH(2, false);
-  }
-#undef VLP_ADAM_LAUNCH
-  return (int)hipGetLastError();
+  const StepArgs s{w, lr, beta1, beta2, eps, wd, step_size, bc2_sqrt, clip_value};
+  return launch_step(true, n, p, g, m, v, s, mode, coef, acc, stream);
 }
 
 VLP_EXPORT int vlp_pack_conv_batch(int dtype, int n, const long long* desc, void* stream) {

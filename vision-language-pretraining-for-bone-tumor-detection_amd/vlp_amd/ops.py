@@ -597,11 +597,24 @@ def cast(x, y):
 
 
 # ---------------- optimizer / packing ----------------
-def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
+def _step(entry, p, g, m, v, lr, beta1, beta2, eps, wd, step, clip=None, accum=None):
+    """One optimizer-step entry point of the library: the bias corrections in fp64 here, then
+    the arguments the entry point takes after them: clip = (coef, clip_value) -> mode (1: coef,
+    2: clip_value, 0: neither), coef, clip_value;  accum = (acc, w) -> acc, w."""
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    lib().vlp_adamw(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
-                    float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5), _s())
+    tail = ()
+    if clip is not None:
+        coef, clip_value = clip
+        tail = (1 if coef is not None else 2 if clip_value is not None else 0, ptr(coef), float(clip_value or 0.0))
+    if accum is not None:
+        tail += (ptr(accum[0]), float(accum[1]))
+    getattr(lib(), entry)(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1), float(beta2),
+                          float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5), *tail, _s())
+
+
+def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
+    _step("vlp_adamw", p, g, m, v, lr, beta1, beta2, eps, wd, step)
 
 
 def grad_sumsq_nparts(n):
@@ -637,11 +650,7 @@ def adamw_clip(p, g, m, v, lr, beta1, beta2, eps, wd, step, coef=None, clip_valu
     fp32 tensor (norm clipping), else clamp(g, -clip_value, clip_value)."""
     if (coef is None) == (clip_value is None):
         raise ValueError("adamw_clip: exactly one of coef / clip_value")
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    lib().vlp_adamw_clip(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
-                         float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
-                         1 if coef is not None else 2, ptr(coef), float(clip_value or 0.0), _s())
+    _step("vlp_adamw_clip", p, g, m, v, lr, beta1, beta2, eps, wd, step, clip=(coef, clip_value))
 
 
 def _f32_flat(name, *ts):
@@ -682,12 +691,7 @@ def adamw_clip_accum(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc, w=1.0, co
     if acc is None and coef is None and clip_value is None:
         raise ValueError("adamw_clip_accum: without an accumulator one of coef / clip_value (else adamw)")
     _f32_flat("adamw_clip_accum", p, g, m, v, *(() if acc is None else (acc,)))
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    mode = 1 if coef is not None else 2 if clip_value is not None else 0
-    lib().vlp_adamw_clip_accum(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
-                               float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
-                               mode, ptr(coef), float(clip_value or 0.0), ptr(acc), float(w), _s())
+    _step("vlp_adamw_clip_accum", p, g, m, v, lr, beta1, beta2, eps, wd, step, clip=(coef, clip_value), accum=(acc, w))
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc=None, w=1.0, coef=None, clip_value=None):
@@ -698,12 +702,7 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, acc=None, w=1.0, coef
     if coef is not None and clip_value is not None:
         raise ValueError("adam_step: at most one of coef / clip_value")
     _f32_flat("adam_step", p, g, m, v, *(() if acc is None else (acc,)))
-    bc1 = 1.0 - beta1 ** step
-    bc2 = 1.0 - beta2 ** step
-    mode = 1 if coef is not None else 2 if clip_value is not None else 0
-    lib().vlp_adam_step(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(beta1),
-                        float(beta2), float(eps), float(wd), float(lr / bc1), float(bc2 ** 0.5),
-                        mode, ptr(coef), float(clip_value or 0.0), ptr(acc), float(w), _s())
+    _step("vlp_adam_step", p, g, m, v, lr, beta1, beta2, eps, wd, step, clip=(coef, clip_value), accum=(acc, w))
 
 
 def pack_conv(w, wp, wt):

@@ -260,22 +260,20 @@ class FusedAdamW(torch.optim.Optimizer):
         ops.clip_coef(off, partials, self._clip[1], out)
         self.last_grad_norm = out[0]
 
-    def _launch(self, arena, o, n, group, step):
+    def _launch(self, arena, o, n, group, step, op=None):
+        """One span's step.  op: the entry point that takes every case (FusedAdam's); None: AdamW's
+        entry point for this case."""
         b1, b2 = group["betas"]
         m, v = self._moments(arena)
         grad = self._accumulator(arena) if self._src == ("acc",) else arena.grad
-        args = (arena.data[o:o + n], grad[o:o + n], m[o:o + n], v[o:o + n],
-                group["lr"], b1, b2, group["eps"], group["weight_decay"], step)
+        kw = {} if self._clip is None else (dict(coef=self._clip_bufs[1][1:]) if self._clip[0] == "norm"
+                                            else dict(clip_value=self._clip[1]))
         if self._src is not None and self._src[0] == "sum":
-            kw = {} if self._clip is None else (dict(coef=self._clip_bufs[1][1:]) if self._clip[0] == "norm"
-                                                else dict(clip_value=self._clip[1]))
-            ops.adamw_clip_accum(*args, acc=self._accumulator(arena)[o:o + n], w=self._src[1], **kw)
-        elif self._clip is None:
-            ops.adamw(*args)
-        elif self._clip[0] == "norm":
-            ops.adamw_clip(*args, coef=self._clip_bufs[1][1:])
-        else:
-            ops.adamw_clip(*args, clip_value=self._clip[1])
+            kw.update(acc=self._accumulator(arena)[o:o + n], w=self._src[1])
+        if op is None:
+            op = ops.adamw_clip_accum if "acc" in kw else ops.adamw_clip if kw else ops.adamw
+        op(arena.data[o:o + n], grad[o:o + n], m[o:o + n], v[o:o + n],
+           group["lr"], b1, b2, group["eps"], group["weight_decay"], step, **kw)
 
     def state_dict(self):
         for group in self.param_groups:
@@ -334,12 +332,4 @@ class FusedAdam(FusedAdamW):
             raise ValueError("FusedAdam: the loaded state asks for amsgrad / maximize")
 
     def _launch(self, arena, o, n, group, step):
-        b1, b2 = group["betas"]
-        m, v = self._moments(arena)
-        grad = self._accumulator(arena) if self._src == ("acc",) else arena.grad
-        kw = {} if self._clip is None else (dict(coef=self._clip_bufs[1][1:]) if self._clip[0] == "norm"
-                                            else dict(clip_value=self._clip[1]))
-        if self._src is not None and self._src[0] == "sum":
-            kw.update(acc=self._accumulator(arena)[o:o + n], w=self._src[1])
-        ops.adam_step(arena.data[o:o + n], grad[o:o + n], m[o:o + n], v[o:o + n],
-                      group["lr"], b1, b2, group["eps"], group["weight_decay"], step, **kw)
+        super()._launch(arena, o, n, group, step, op=ops.adam_step)
