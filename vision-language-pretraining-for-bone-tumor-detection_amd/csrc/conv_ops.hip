@@ -1503,10 +1503,9 @@ static bool rows_c64_ok(const ConvGeom& g) {
 template <class EP, int XF = 0>
 static int launch_rows_c64(const ConvGeom& g, const void* x, const void* w, int flip, const EP& ep,
                            hipStream_t st, const RowsXIn& xin = RowsXIn{}) {
-  // per device and cheap: set on every launch (a process-wide flag would miss a second GPU)
-  const hipError_t ae = hipFuncSetAttribute((const void*)&conv3x3_c64_rows_kernel<EP, XF>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, kRcLds);
-  if (ae != hipSuccess) return (int)ae;
+  static KernelDevState kst;
+  const int e = prepare_kernel(kst, (const void*)&conv3x3_c64_rows_kernel<EP, XF>, kRcLds, 0, nullptr);
+  if (e) return e;
   int grid = device_cus();
   if (grid > g.N) grid = g.N;
   hipLaunchKernelGGL((conv3x3_c64_rows_kernel<EP, XF>), dim3(grid), dim3(512), kRcLds, st, g.N, g.H,
@@ -1744,9 +1743,9 @@ static bool wgrad_rows_ok(const ConvGeom& g) {
 // one slab per workgroup: grid <= the slabs the workspace holds
 static int launch_wgrad_rows(const ConvGeom& g, const void* dy, const void* x, float* ws, int max_ks, int* ks_out,
                              hipStream_t st) {
-  const hipError_t ae = hipFuncSetAttribute((const void*)&conv3x3_c64_wgrad_rows_kernel,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, kRwLds);
-  if (ae != hipSuccess) return (int)ae;
+  static KernelDevState kst;
+  const int e = prepare_kernel(kst, (const void*)&conv3x3_c64_wgrad_rows_kernel, kRwLds, 0, nullptr);
+  if (e) return e;
   int grid = device_cus();
   if (grid > g.N) grid = g.N;
   if (grid > max_ks) grid = max_ks;
@@ -2070,106 +2069,97 @@ static int conv_fwd_t(const void* x, const void* wp, void* y, ConvGeom g, const 
   return gemm_auto<T>(g.M, g.Co, g.K, 1, la, lb, ep, st);
 }
 
+// ---- data-gradient host dispatch: every vlp_conv_dgrad* entry point routes through here ----
+// the GEMM view of a data gradient: rows = input pixels, reduction = (filter tap, Co)
+static ConvGeom dgrad_geom(ConvGeom g) {
+  g.M = g.N * g.H * g.W;
+  g.K = g.KH * g.KW * g.Co;
+  return g;
+}
+// stride 1 = forward conv of dy with the flipped, transposed filter: the layer-1
+// rows kernel, then the LDS-window kernel, then the im2col GEMM
+template <typename T, class EP>
+static int dgrad_s1(const ConvGeom& g, const void* dy, const void* wt, const EP& ep, hipStream_t st) {
+  if constexpr (std::is_same<T, bf16>::value) {
+    if constexpr (!Stat3Trait<EP>::value) {   // the rows kernel has no three-sum epilogue form
+      if (rows_c64_ok(g)) return launch_rows_c64(g, dy, wt, 1, ep, st);
+    }
+    if (VLP_WIN && win_ok(g, g.Co, g.C)) return launch_win<true>(g, g.Co, g.C, dy, wt, ep, st);
+  }
+  ConvDgradA<T> la{g, (const T*)dy};
+  KMat<T> lb{(const T*)wt, g.K, g.C, g.K};
+  return gemm_auto<T>(g.M, g.C, g.K, 1, la, lb, ep, st);
+}
+// stride 2: four parity classes, each a dense GEMM over its valid taps only.
+// dd_off / wd_off: the downsample fold (ConvDgradS2A), whose 1x1/2 data gradient
+// lands on the (0, 0) pixels only
+template <typename T, class EP>
+static int dgrad_s2(const ConvGeom& g, const void* dy, const void* wt, const EP& in, double* s1, double* s2, int rep,
+                    hipStream_t st, long long dd_off = 0, long long wd_off = 0) {
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      S2Class c = make_s2class(g, ph, pw);
+      const int Mc = g.N * c.Hc * c.Wc, Kc1 = c.nth * c.ntw * g.Co;
+      if (Mc <= 0) continue;
+      const bool fold = dd_off && ph == 0 && pw == 0;
+      const int Kc = Kc1 + (fold ? g.Co : 0);
+      ConvDgradS2A<T> la{g, c, (const T*)dy, Mc, Kc};
+      WtS2B<T> lb{(const T*)wt, g, c, Kc};
+      if (fold) {
+        la.Kc1 = Kc1; la.dd_off = dd_off;
+        lb.Kc1 = Kc1; lb.wd_off = wd_off;
+      }
+      EpiS2Remap<EP> ep{s1, s2, rep, in, c, g.H, g.W};
+      const int r = gemm_s2<T>(Mc, g.C, Kc, la, lb, ep, st);
+      if (r) return r;
+    }
+  return 0;
+}
+template <typename T, class EP>
+static int dgrad_route(const ConvGeom& g, const void* dy, const void* wt, const EP& ep, double* s1, double* s2,
+                       int rep, hipStream_t st, long long dd_off = 0, long long wd_off = 0) {
+  if (g.S == 2) return dgrad_s2<T>(g, dy, wt, ep, s1, s2, rep, st, dd_off, wd_off);
+  return dgrad_s1<T>(g, dy, wt, ep, st);
+}
+
+// operands of the ReLU-masked epilogue (EpiDgradRelu), as the entry points receive them
+struct DgradReluArgs {
+  void* gout; const void* addend; const void* relu_out; const uint8_t* relu_mask; const void* y;
+  const float* mean; const float* invstd; double* s1; double* s2; int rep;
+};
+// f(epilogue): the sign-bit instantiation when relu_mask is set, else the activation's
+template <typename T, class F>
+static int with_dgrad_relu_epi(const DgradReluArgs& a, int C, F&& f) {
+  auto ep = [&](auto bits) {
+    return EpiDgradRelu<T, decltype(bits)::value>{a.s1, a.s2, a.rep, (T*)a.gout, (const T*)a.addend, C,
+                                                  (const T*)a.relu_out, (const T*)a.y, a.mean, a.invstd,
+                                                  a.relu_mask};
+  };
+  return a.relu_mask ? f(ep(std::true_type{})) : f(ep(std::false_type{}));
+}
+
 template <typename T>
 static int conv_dgrad_t(const void* dy, const void* wt, void* dx, ConvGeom g, const void* addend,
                         const void* ybn, const float* sc, const float* sh, const float* mean,
                         const float* invstd, double* s1, double* s2, int rep, hipStream_t st) {
-  g.M = g.N * g.H * g.W;
-  g.K = g.KH * g.KW * g.Co;
+  g = dgrad_geom(g);
   if (std::is_same<T, bf16>::value && g.Co % 64) return (int)hipErrorInvalidValue;   // one tap per K-step
-  if (g.S == 2) {
-    // four parity classes, each a dense GEMM over its valid taps only
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw) {
-        S2Class c = make_s2class(g, ph, pw);
-        const int Mc = g.N * c.Hc * c.Wc, Kc = c.nth * c.ntw * g.Co;
-        if (Mc <= 0) continue;
-        ConvDgradS2A<T> la{g, c, (const T*)dy, Mc, Kc};
-        WtS2B<T> lb{(const T*)wt, g, c, Kc};
-        int r;
-        if (ybn) {
-          EpiDgradBN<T> in{s1, s2, rep, (T*)dx, g.C, (const T*)ybn, sc, sh, mean, invstd};
-          EpiS2Remap<EpiDgradBN<T>> ep{s1, s2, rep, in, c, g.H, g.W};
-          r = gemm_s2<T>(Mc, g.C, Kc, la, lb, ep, st);
-        } else {
-          EpiDgradAdd<T> in{nullptr, nullptr, (T*)dx, (const T*)addend, g.C};
-          EpiS2Remap<EpiDgradAdd<T>> ep{nullptr, nullptr, 1, in, c, g.H, g.W};
-          r = gemm_s2<T>(Mc, g.C, Kc, la, lb, ep, st);
-        }
-        if (r) return r;
-      }
-    return 0;
-  }
-  ConvDgradA<T> la{g, (const T*)dy};
-  KMat<T> lb{(const T*)wt, g.K, g.C, g.K};
-  // stride-1 dgrad = forward conv of dy with the flipped, transposed filter
-  const bool rows = std::is_same<T, bf16>::value && rows_c64_ok(g);
-  const bool win = std::is_same<T, bf16>::value && VLP_WIN && win_ok(g, g.Co, g.C);
   if (ybn) {
     EpiDgradBN<T> ep{s1, s2, rep, (T*)dx, g.C, (const T*)ybn, sc, sh, mean, invstd};
-    if constexpr (std::is_same<T, bf16>::value) {
-      if (rows) return launch_rows_c64(g, dy, wt, 1, ep, st);
-      if (win) return launch_win<true>(g, g.Co, g.C, dy, wt, ep, st);
-    }
-    return gemm_auto<T>(g.M, g.C, g.K, 1, la, lb, ep, st);
+    return dgrad_route<T>(g, dy, wt, ep, s1, s2, rep, st);
   }
   EpiDgradAdd<T> ep{nullptr, nullptr, (T*)dx, (const T*)addend, g.C};
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (rows) return launch_rows_c64(g, dy, wt, 1, ep, st);
-    if (win) return launch_win<true>(g, g.Co, g.C, dy, wt, ep, st);
-  }
-  return gemm_auto<T>(g.M, g.C, g.K, 1, la, lb, ep, st);
+  return dgrad_route<T>(g, dy, wt, ep, nullptr, nullptr, 1, st);
 }
 
 // dgrad whose output is masked by a ReLU output and reduced for a BN backward
-template <typename T, bool BITS>
-static int conv_dgrad_relu_impl(const void* dy, const void* wt, void* gout, ConvGeom g0, const void* addend,
-                                const void* relu_out, const uint8_t* relu_mask, const void* y, const float* mean,
-                                const float* invstd, double* s1, double* s2, int rep, hipStream_t st,
-                                long long dd_off = 0, long long wd_off = 0) {
-  ConvGeom g = g0;
-  g.M = g.N * g.H * g.W;
-  g.K = g.KH * g.KW * g.Co;
-  EpiDgradRelu<T, BITS> in{s1, s2, rep, (T*)gout, (const T*)addend, g.C, (const T*)relu_out, (const T*)y, mean,
-                           invstd, relu_mask};
-  if (g.S == 2) {
-    for (int ph = 0; ph < 2; ++ph)
-      for (int pw = 0; pw < 2; ++pw) {
-        S2Class c = make_s2class(g, ph, pw);
-        const int Mc = g.N * c.Hc * c.Wc, Kc1 = c.nth * c.ntw * g.Co;
-        if (Mc <= 0) continue;
-        // the downsample's 1x1/2 data gradient lands on the (0, 0) pixels only
-        const bool fold = dd_off && ph == 0 && pw == 0;
-        const int Kc = Kc1 + (fold ? g.Co : 0);
-        ConvDgradS2A<T> la{g, c, (const T*)dy, Mc, Kc};
-        WtS2B<T> lb{(const T*)wt, g, c, Kc};
-        if (fold) {
-          la.Kc1 = Kc1; la.dd_off = dd_off;
-          lb.Kc1 = Kc1; lb.wd_off = wd_off;
-        }
-        EpiS2Remap<EpiDgradRelu<T, BITS>> ep{s1, s2, rep, in, c, g.H, g.W};
-        const int r = gemm_s2<T>(Mc, g.C, Kc, la, lb, ep, st);
-        if (r) return r;
-      }
-    return 0;
-  }
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (rows_c64_ok(g)) return launch_rows_c64(g, dy, wt, 1, in, st);
-    if (VLP_WIN && win_ok(g, g.Co, g.C)) return launch_win<true>(g, g.Co, g.C, dy, wt, in, st);
-  }
-  ConvDgradA<T> la{g, (const T*)dy};
-  KMat<T> lb{(const T*)wt, g.K, g.C, g.K};
-  return gemm_auto<T>(g.M, g.C, g.K, 1, la, lb, in, st);
-}
 template <typename T>
-static int conv_dgrad_relu_t(const void* dy, const void* wt, void* gout, ConvGeom g0, const void* addend,
-                             const void* relu_out, const uint8_t* relu_mask, const void* y, const float* mean,
-                             const float* invstd, double* s1, double* s2, int rep, hipStream_t st) {
-  if (relu_mask)
-    return conv_dgrad_relu_impl<T, true>(dy, wt, gout, g0, addend, relu_out, relu_mask, y, mean, invstd, s1, s2,
-                                         rep, st);
-  return conv_dgrad_relu_impl<T, false>(dy, wt, gout, g0, addend, relu_out, relu_mask, y, mean, invstd, s1, s2,
-                                        rep, st);
+static int conv_dgrad_relu_t(const void* dy, const void* wt, ConvGeom g, const DgradReluArgs& a, hipStream_t st,
+                             long long dd_off = 0, long long wd_off = 0) {
+  g = dgrad_geom(g);
+  return with_dgrad_relu_epi<T>(a, g.C, [&](const auto& ep) {
+    return dgrad_route<T>(g, dy, wt, ep, a.s1, a.s2, a.rep, st, dd_off, wd_off);
+  });
 }
 
 template <typename T>
@@ -2487,6 +2477,13 @@ static RowsXIn rows_bwd_xin(const void* y_in, const float* in_coef, void* dy_out
   xin.out = (bf16*)dy_out;
   return xin;
 }
+// the one launch of both _act entry points (vlp_conv_dgrad_act_ok shapes only)
+template <class EP>
+static int dgrad_rows_act(const ConvGeom& g, const void* g_in, const void* y_in, const float* in_coef,
+                          void* dy_out, const void* wt, const EP& ep, void* stream) {
+  return launch_rows_c64<EP, 2>(dgrad_geom(g), g_in, wt, 1, ep, (hipStream_t)stream,
+                                rows_bwd_xin(y_in, in_coef, dy_out));
+}
 
 VLP_EXPORT int vlp_conv_dgrad_act_ok(int dtype, int N, int H, int W, int C, int Co, int KH, int KW, int S,
                                     int P) {
@@ -2502,13 +2499,9 @@ VLP_EXPORT int vlp_conv_dgrad_bn_act(int dtype, const void* g_in, const void* y_
   if (!vlp_conv_dgrad_act_ok(dtype, N, H, W, C, Co, KH, KW, S, P) || !g_in || !y_in || !dy_out || !in_coef ||
       !y_bn || !bn_scale || !bn_shift || !bn_mean || !bn_invstd || !stat1 || !stat2)
     return (int)hipErrorInvalidValue;
-  ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
-  g.M = g.N * g.H * g.W;
-  g.K = g.KH * g.KW * g.Co;
-  EpiDgradBN<bf16> ep{stat1, stat2, stat_rep, (bf16*)dx, g.C, (const bf16*)y_bn, bn_scale, bn_shift, bn_mean,
+  EpiDgradBN<bf16> ep{stat1, stat2, stat_rep, (bf16*)dx, C, (const bf16*)y_bn, bn_scale, bn_shift, bn_mean,
                       bn_invstd};
-  return launch_rows_c64<EpiDgradBN<bf16>, 2>(g, g_in, wt, 1, ep, (hipStream_t)stream,
-                                              rows_bwd_xin(y_in, in_coef, dy_out));
+  return dgrad_rows_act(make_geom(N, H, W, C, Co, KH, KW, S, P), g_in, y_in, in_coef, dy_out, wt, ep, stream);
 }
 
 VLP_EXPORT int vlp_conv_dgrad_relu_act(int dtype, const void* g_in, const void* y_in, const float* in_coef,
@@ -2521,19 +2514,11 @@ VLP_EXPORT int vlp_conv_dgrad_relu_act(int dtype, const void* g_in, const void* 
       (relu_out == nullptr) == (relu_mask == nullptr) || !y ||
       !mean || !invstd || !stat1 || !stat2)
     return (int)hipErrorInvalidValue;
-  ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
-  g.M = g.N * g.H * g.W;
-  g.K = g.KH * g.KW * g.Co;
-  const RowsXIn xin = rows_bwd_xin(y_in, in_coef, dy_out);
-  hipStream_t st = (hipStream_t)stream;
-  if (relu_mask) {
-    EpiDgradRelu<bf16, true> ep{stat1, stat2, stat_rep, (bf16*)gout, (const bf16*)addend, g.C,
-                                (const bf16*)relu_out, (const bf16*)y, mean, invstd, relu_mask};
-    return launch_rows_c64<EpiDgradRelu<bf16, true>, 2>(g, g_in, wt, 1, ep, st, xin);
-  }
-  EpiDgradRelu<bf16, false> ep{stat1, stat2, stat_rep, (bf16*)gout, (const bf16*)addend, g.C,
-                               (const bf16*)relu_out, (const bf16*)y, mean, invstd, relu_mask};
-  return launch_rows_c64<EpiDgradRelu<bf16, false>, 2>(g, g_in, wt, 1, ep, st, xin);
+  const ConvGeom g = make_geom(N, H, W, C, Co, KH, KW, S, P);
+  const DgradReluArgs a{gout, addend, relu_out, relu_mask, y, mean, invstd, stat1, stat2, stat_rep};
+  return with_dgrad_relu_epi<bf16>(a, C, [&](const auto& ep) {
+    return dgrad_rows_act(g, g_in, y_in, in_coef, dy_out, wt, ep, stream);
+  });
 }
 
 VLP_EXPORT int vlp_conv_dgrad(int dtype, const void* dy, const void* wt, void* dx, int N, int H,
@@ -2561,11 +2546,9 @@ VLP_EXPORT int vlp_conv_dgrad_relu(int dtype, const void* dy, const void* wt, vo
   hipStream_t st = (hipStream_t)stream;
   if ((relu_out == nullptr) == (relu_mask == nullptr) || C % 8 || !conv_chunks_ok(dtype, C, Co))
     return (int)hipErrorInvalidValue;
-  if (dtype == VLP_BF16)
-    return conv_dgrad_relu_t<bf16>(dy, wt, g, geo, addend, relu_out, relu_mask, y, mean, invstd, stat1, stat2,
-                                   stat_rep, st);
-  return conv_dgrad_relu_t<float>(dy, wt, g, geo, addend, relu_out, relu_mask, y, mean, invstd, stat1, stat2,
-                                  stat_rep, st);
+  const DgradReluArgs a{g, addend, relu_out, relu_mask, y, mean, invstd, stat1, stat2, stat_rep};
+  if (dtype == VLP_BF16) return conv_dgrad_relu_t<bf16>(dy, wt, geo, a, st);
+  return conv_dgrad_relu_t<float>(dy, wt, geo, a, st);
 }
 
 // The second block of layers 2-4: conv1's data gradient (+ the identity
@@ -2581,15 +2564,9 @@ VLP_EXPORT int vlp_conv_dgrad_relu2(int dtype, const void* dy, const void* wt, v
   if (dtype != VLP_BF16 || S != 1 || C < 128 || C % 64 || Co % 64 || !relu_mask || !y ||
       !yd || !mean || !invstd || !meand || !invstdd || !stat1 || !stat2 || !stat3)
     return (int)hipErrorInvalidValue;
-  ConvGeom g1 = g0;
-  g1.M = g1.N * g1.H * g1.W;
-  g1.K = g1.KH * g1.KW * g1.Co;
-  EpiDgradRelu2<bf16> ep{stat1, stat2, stat_rep, stat3, (bf16*)g, (const bf16*)addend, g1.C, relu_mask,
+  EpiDgradRelu2<bf16> ep{stat1, stat2, stat_rep, stat3, (bf16*)g, (const bf16*)addend, C, relu_mask,
                          (const bf16*)y, (const bf16*)yd, mean, invstd, meand, invstdd};
-  if (VLP_WIN && win_ok(g1, g1.Co, g1.C)) return launch_win<true>(g1, g1.Co, g1.C, dy, wt, ep, (hipStream_t)stream);
-  ConvDgradA<bf16> la{g1, (const bf16*)dy};
-  KMat<bf16> lb{(const bf16*)wt, g1.K, g1.C, g1.K};
-  return gemm_auto<bf16>(g1.M, g1.C, g1.K, 1, la, lb, ep, (hipStream_t)stream);
+  return dgrad_s1<bf16>(dgrad_geom(g0), dy, wt, ep, (hipStream_t)stream);
 }
 
 // Stride-2 block entry (layers 2-4, block 0): conv1's 3x3/2 data gradient with the
@@ -2608,12 +2585,8 @@ VLP_EXPORT int vlp_conv_dgrad_relu_ds(int dtype, const void* dy, const void* dyd
       (relu_out == nullptr) == (relu_mask == nullptr) || (const bf16*)dyd != (const bf16*)dy + dd ||
       (const bf16*)wtd != (const bf16*)wt + wd || (size_t)2 * dd * 2 >= (1ull << 32))
     return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  if (relu_mask)
-    return conv_dgrad_relu_impl<bf16, true>(dy, wt, g, geo, nullptr, relu_out, relu_mask, y, mean, invstd, stat1,
-                                            stat2, stat_rep, st, dd, wd);
-  return conv_dgrad_relu_impl<bf16, false>(dy, wt, g, geo, nullptr, relu_out, relu_mask, y, mean, invstd, stat1,
-                                           stat2, stat_rep, st, dd, wd);
+  const DgradReluArgs a{g, nullptr, relu_out, relu_mask, y, mean, invstd, stat1, stat2, stat_rep};
+  return conv_dgrad_relu_t<bf16>(dy, wt, geo, a, (hipStream_t)stream, dd, wd);
 }
 
 VLP_EXPORT int vlp_conv_wgrad(int dtype, const void* dy, const void* x, float* dw_ws, int N, int H,

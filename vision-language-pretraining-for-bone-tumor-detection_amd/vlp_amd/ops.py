@@ -76,21 +76,32 @@ def conv_fwd_act(x, wp, Co, KH, KW, S, P, in_scale, in_shift, x_act, stat_sum, s
     return y
 
 
+def _conv_dgrad(entry, label, pre, geom, post, stat_rep, out, relu=None, post2=(), taps=None):
+    """The shared body of the conv_dgrad* wrappers:
+    vlp_<entry>(dtype, *pre, out, N, H, W, C, Co, KH, KW, S, P, *post, [relu_out, relu_mask,] *post2, stat_rep, stream)
+    timed under `label`.  pre[0] is the [N][Ho][Wo][Co] gradient; `relu` is the ReLU
+    activation or its uint8 sign-bit mask and fills the one pointer of the pair it is."""
+    dy = pre[0]
+    H, W, C, KH, KW, S, P = geom
+    N, Ho, Wo, Co = dy.shape
+    if out is None:
+        out = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    if relu is not None:
+        bits = relu.dtype == torch.uint8
+        post = (*post, None if bits else relu, relu if bits else None)
+    tk = ktimer.begin(label, 2.0 * N * Ho * Wo * Co * C * (taps or KH * KW))
+    getattr(lib(), "vlp_" + entry)(dcode(dy), *map(ptr, pre), ptr(out), N, H, W, C, Co, KH, KW, S, P,
+                                   *map(ptr, post), *map(ptr, post2), int(stat_rep), _s())
+    ktimer.end(tk)
+    return out
+
+
 def conv_dgrad(dy, wt, H, W, C, KH, KW, S, P, addend=None, y_bn=None, bn=None, stat1=None,
                stat2=None, out=None, stat_rep=1):
     """bn = (scale, shift, mean, invstd) of the BN+ReLU producing the conv input."""
-    N, Ho, Wo, Co = dy.shape
-    dx = out if out is not None else torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-    sc = sh = mu = ist = None
-    if y_bn is not None:
-        sc, sh, mu, ist = bn
-    tk = ktimer.begin(f"conv_dgrad[{'bn' if y_bn is not None else 'add'}]{_tile_auto(C)}",
-                      2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_dgrad(dcode(dy), ptr(dy), ptr(wt), ptr(dx), N, H, W, C, Co, KH, KW, S, P,
-                         ptr(addend), ptr(y_bn), ptr(sc), ptr(sh), ptr(mu), ptr(ist), ptr(stat1),
-                         ptr(stat2), int(stat_rep), _s())
-    ktimer.end(tk)
-    return dx
+    bn = bn if y_bn is not None else (None,) * 4
+    return _conv_dgrad("conv_dgrad", f"conv_dgrad[{'bn' if y_bn is not None else 'add'}]{_tile_auto(C)}",
+                       (dy, wt), (H, W, C, KH, KW, S, P), (addend, y_bn, *bn, stat1, stat2), stat_rep, out)
 
 
 def conv_dgrad_relu(dy, wt, H, W, C, KH, KW, S, P, relu_out, y, mean, invstd, stat1, stat2,
@@ -98,15 +109,8 @@ def conv_dgrad_relu(dy, wt, H, W, C, KH, KW, S, P, relu_out, y, mean, invstd, st
     """g = (dgrad(dy) + addend) * (relu_out > 0), plus the BN backward sums of g
     against y (the next block's bn2 input).  relu_out may be the activation or
     its uint8 sign-bit mask (bn_add_relu / maxpool_fwd relu_mask)."""
-    N, Ho, Wo, Co = dy.shape
-    g = out if out is not None else torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-    bits = relu_out.dtype == torch.uint8
-    tk = ktimer.begin(f"conv_dgrad[relu]{_tile_auto(C)}", 2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_dgrad_relu(dcode(dy), ptr(dy), ptr(wt), ptr(g), N, H, W, C, Co, KH, KW, S, P,
-                              ptr(addend), None if bits else ptr(relu_out), ptr(relu_out) if bits else None,
-                              ptr(y), ptr(mean), ptr(invstd), ptr(stat1), ptr(stat2), int(stat_rep), _s())
-    ktimer.end(tk)
-    return g
+    return _conv_dgrad("conv_dgrad_relu", f"conv_dgrad[relu]{_tile_auto(C)}", (dy, wt), (H, W, C, KH, KW, S, P),
+                       (addend,), stat_rep, out, relu_out, (y, mean, invstd, stat1, stat2))
 
 
 def conv_dgrad_act_ok(dy, C, KH, KW, S, P):
@@ -125,31 +129,16 @@ def conv_dgrad_bn_act(g_in, y_in, in_coef, dy_out, wt, H, W, C, KH, KW, S, P, y_
     """conv_dgrad(dy, y_bn=..., bn=...) with dy = k*g_in + b*y_in + c formed in the
     layer-1 rows kernel's ring from in_coef (bn_bwd_coef) and written to dy_out
     (vlp_conv_dgrad_bn_act: the bn_bwd_apply pass fused)."""
-    N, Ho, Wo, Co = g_in.shape
-    dx = out if out is not None else torch.empty((N, H, W, C), dtype=g_in.dtype, device=g_in.device)
-    sc, sh, mu, ist = bn
-    tk = ktimer.begin("conv_dgrad[bn,act]/narrow", 2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_dgrad_bn_act(dcode(g_in), ptr(g_in), ptr(y_in), ptr(in_coef), ptr(dy_out), ptr(wt), ptr(dx),
-                                N, H, W, C, Co, KH, KW, S, P, ptr(y_bn), ptr(sc), ptr(sh), ptr(mu), ptr(ist),
-                                ptr(stat1), ptr(stat2), int(stat_rep), _s())
-    ktimer.end(tk)
-    return dx
+    return _conv_dgrad("conv_dgrad_bn_act", "conv_dgrad[bn,act]/narrow", (g_in, y_in, in_coef, dy_out, wt),
+                       (H, W, C, KH, KW, S, P), (y_bn, *bn, stat1, stat2), stat_rep, out)
 
 
 def conv_dgrad_relu_act(g_in, y_in, in_coef, dy_out, wt, H, W, C, KH, KW, S, P, relu_out, y, mean, invstd,
                         stat1, stat2, addend=None, stat_rep=1, out=None):
     """conv_dgrad_relu with its input dy = k*g_in + b*y_in + c formed in the rows
     kernel's ring and written to dy_out (vlp_conv_dgrad_relu_act)."""
-    N, Ho, Wo, Co = g_in.shape
-    g = out if out is not None else torch.empty((N, H, W, C), dtype=g_in.dtype, device=g_in.device)
-    bits = relu_out.dtype == torch.uint8
-    tk = ktimer.begin("conv_dgrad[relu,act]/narrow", 2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_dgrad_relu_act(dcode(g_in), ptr(g_in), ptr(y_in), ptr(in_coef), ptr(dy_out), ptr(wt), ptr(g),
-                                  N, H, W, C, Co, KH, KW, S, P, ptr(addend), None if bits else ptr(relu_out),
-                                  ptr(relu_out) if bits else None, ptr(y), ptr(mean), ptr(invstd), ptr(stat1),
-                                  ptr(stat2), int(stat_rep), _s())
-    ktimer.end(tk)
-    return g
+    return _conv_dgrad("conv_dgrad_relu_act", "conv_dgrad[relu,act]/narrow", (g_in, y_in, in_coef, dy_out, wt),
+                       (H, W, C, KH, KW, S, P), (addend,), stat_rep, out, relu_out, (y, mean, invstd, stat1, stat2))
 
 
 def conv_dgrad_relu_ds(dy, dyd, wt, wtd, H, W, C, KH, KW, S, P, relu_out, y, mean, invstd, stat1, stat2,
@@ -157,16 +146,9 @@ def conv_dgrad_relu_ds(dy, dyd, wt, wtd, H, W, C, KH, KW, S, P, relu_out, y, mea
     """conv_dgrad_relu of a stride-2 conv with the 1x1/2 downsample's data gradient
     (dyd against wtd) folded into parity class (0, 0) in the same GEMMs
     (vlp_conv_dgrad_relu_ds).  dyd must follow dy and wtd follow wt in memory."""
-    N, Ho, Wo, Co = dy.shape
-    g = out if out is not None else torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-    bits = relu_out.dtype == torch.uint8
-    flops = 2.0 * N * Ho * Wo * Co * C * (KH * KW + 1)
-    tk = ktimer.begin(f"conv_dgrad[relu,ds]{_tile_auto(C)}", flops)
-    lib().vlp_conv_dgrad_relu_ds(dcode(dy), ptr(dy), ptr(dyd), ptr(wt), ptr(wtd), ptr(g), N, H, W, C, Co, KH, KW, S,
-                                 P, None if bits else ptr(relu_out), ptr(relu_out) if bits else None, ptr(y),
-                                 ptr(mean), ptr(invstd), ptr(stat1), ptr(stat2), int(stat_rep), _s())
-    ktimer.end(tk)
-    return g
+    return _conv_dgrad("conv_dgrad_relu_ds", f"conv_dgrad[relu,ds]{_tile_auto(C)}", (dy, dyd, wt, wtd),
+                       (H, W, C, KH, KW, S, P), (), stat_rep, out, relu_out, (y, mean, invstd, stat1, stat2),
+                       taps=KH * KW + 1)
 
 
 def conv_dgrad_relu2(dy, wt, H, W, C, KH, KW, S, P, relu_mask, y, mean, invstd, yd, meand, invstdd,
@@ -174,14 +156,8 @@ def conv_dgrad_relu2(dy, wt, H, W, C, KH, KW, S, P, relu_mask, y, mean, invstd, 
     """g = (dgrad(dy) + addend) * relu bits, with the three BN backward sums of a
     block whose output feeds its bn2 (y, mean, invstd) and its downsample BN (yd,
     meand, invstdd): sum g, sum g*xhat, sum g*xhatd (vlp_conv_dgrad_relu2)."""
-    N, Ho, Wo, Co = dy.shape
-    g = out if out is not None else torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
-    tk = ktimer.begin(f"conv_dgrad[relu2]{_tile_auto(C)}", 2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_dgrad_relu2(dcode(dy), ptr(dy), ptr(wt), ptr(g), N, H, W, C, Co, KH, KW, S, P, ptr(addend),
-                               ptr(relu_mask), ptr(y), ptr(mean), ptr(invstd), ptr(yd), ptr(meand), ptr(invstdd),
-                               ptr(stat1), ptr(stat2), ptr(stat3), int(stat_rep), _s())
-    ktimer.end(tk)
-    return g
+    return _conv_dgrad("conv_dgrad_relu2", f"conv_dgrad[relu2]{_tile_auto(C)}", (dy, wt), (H, W, C, KH, KW, S, P),
+                       (addend, relu_mask, y, mean, invstd, yd, meand, invstdd, stat1, stat2, stat3), stat_rep, out)
 
 
 def conv_wgrad(dy, x, KH, KW, S, P, dw_ws, in_scale=None, in_shift=None):
