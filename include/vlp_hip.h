@@ -412,6 +412,43 @@ int vlp_row_topk(int R, int N, const float* x, long long ldx, int K, float* vals
 int vlp_cluster_dist_sums(int Q, int N, int D, const float* xq, long long ldq, const float* xk,
                           long long ldk, const int* key_label, int C, float* sums, void* stream);
 
+/* ---------------- post-fit t-SNE ----------------
+ * Replace sklearn.manifold.TSNE(method="exact") over the best checkpoint's cached features in
+ * plot_tsne_and_calculate_silhouette.py:62-66.  Every N below is at most 32768 (P [N][N] fp32
+ * stays within 4 GB); no atomics, every sum in one fixed order: two runs agree bit for bit.  A NULL
+ * pointer or a size out of range is hipErrorInvalidValue with nothing launched.
+ *
+ * vlp_tsne_sqdist: d2[i][j] = sum_d (x[i][d] - x[j][d])^2 from direct fp32 differences, any D >= 1:
+ * an exactly zero diagonal (and zeros between duplicate rows), nothing negative, symmetric bit for
+ * bit.  ldx >= D, ldd >= N.
+ *
+ * vlp_tsne_affinities: sklearn's _joint_probabilities on d2 [N][ldd].  Per row (one wave each)
+ * _binary_search_perplexity in fp64: beta from 1, infinite bounds doubled / halved, at most 100
+ * steps, |H - log(perplexity)| <= 1e-5, no diagonal, a zero row sum replaced by 1e-8.  cond [N][N]
+ * fp32 (dense, written) is the conditional matrix, ws holds N + 1 doubles of scratch, and
+ * P[i][j] = max((cond[i][j] + cond[j][i]) / max(sum, eps), eps) with eps = 2^-52 and a zero
+ * diagonal (dense [N][N] fp32; symmetric bit for bit).  2 <= N, 0 < perplexity < N.
+ *
+ * vlp_tsne_pairs: the all-pairs pass of one iteration over Y [N][2] and P [N][N].  With
+ * d = y_i - y_j and q = 1 / (1 + |d|^2) (fp32), the sums over j != i, accumulated in fp64:
+ * parts[i][0..7) = { q, p q d_0, p q d_1, q^2 d_0, q^2 d_1, p (log p + log(1 + |d|^2)), p };
+ * the last two only when check != 0 (0 otherwise), from a second instantiation of the kernel.
+ *
+ * vlp_tsne_update: one step of sklearn's _gradient_descent from parts (one workgroup).
+ * Z = sum_i parts[i][0]; grad = (float)(4 (exag attr - rep / Z)); where update * grad < 0 the
+ * gain += 0.2, elsewhere *= 0.8, floored at 0.01; grad *= gain; update = momentum * update -
+ * lr * grad; Y += update -- every fp32 operation rounded on its own, as numpy's.  exag is the
+ * early exaggeration of this iteration (P is never rescaled).  When check != 0, stats[0] = the KL
+ * divergence sum_i parts[i][5] + log(Z) sum_i parts[i][6] of the Y the step started from, and
+ * stats[1] = the norm of the gained gradient (what _gradient_descent compares with
+ * min_grad_norm); these two doubles are the only values the host reads during the descent. */
+int vlp_tsne_sqdist(int N, int D, const float* x, long long ldx, float* d2, long long ldd, void* stream);
+int vlp_tsne_affinities(int N, const float* d2, long long ldd, double perplexity, float* cond,
+                        double* ws, float* P, void* stream);
+int vlp_tsne_pairs(int N, const float* Y, const float* P, double* parts, int check, void* stream);
+int vlp_tsne_update(int N, const double* parts, float* Y, float* update, float* gains, float exag,
+                    float momentum, float lr, int check, double* stats, void* stream);
+
 /* ---------------- NesT image encoder (BASELINE configs[3]) ----------------
  * Replace timm nest.py's pieces behind ImageEncoder's timm.create_model("nest_small", ...)
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,

@@ -20,7 +20,8 @@ fc, the 15->32->20->10 tabular MLP with BatchNorm1d, the 20->1 combination and
 the loss (a few kFLOP per sample) run as device tensor ops.
 
 Not built: the vit / resnet50 / nest_small / torchxrayvision backbones
-(NotImplementedError), torchmetrics accuracy/AUROC logging, t-SNE plots.
+(NotImplementedError), torchmetrics accuracy/AUROC logging.  The t-SNE of the image features is part
+of the post-fit evaluation (src/utils/post_fit_evaluation.py, `post_fit_tsne`).
 Pretrained VLP checkpoints load with torch.load(weights_only=True) (the
 reference uses weights_only=False, :84).
 """

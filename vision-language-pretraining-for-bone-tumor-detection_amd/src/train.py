@@ -22,9 +22,12 @@ features by tumour label and by source dataset and the confusion matrix, for the
 validation and train loaders.  The reference gates it on a W&B logger; here the
 top-level key `post_fit_evaluation: true` turns it on (absent = off), e.g.
 `experiment=baseline_only_imaging/baseline_only_imaging_resnet_34_mi355x_eval`, and the
-numbers join the fold's metrics (src/utils/post_fit_evaluation.py).
+numbers join the fold's metrics (src/utils/post_fit_evaluation.py).  With
+`post_fit_tsne: true` as well (absent = off, `..._mi355x_eval_tsne`) the evaluation
+also computes the reference's 2-D t-SNE of those features on the device, adds
+`tsne_kl_{split}` and writes `tsne_{split}.npz` / `.png` beside the best checkpoint.
 Out of scope: W&B loggers (configured loggers whose package is
-absent are skipped with a warning), the t-SNE and confusion-matrix figures and
+absent are skipped with a warning), the confusion-matrix figure and
 downstream zero-shot evaluation.
 
 Multi-GPU: launch one process per GPU (`python -m torch.distributed.run
@@ -181,7 +184,8 @@ def train(cfg: Dict[str, Any]) -> Tuple[Dict[str, Any], Dict[str, Any]]:
                     fold_metrics[f"downstream_entire/label_precision_at_{k}"] = v
         elif cfg.get("post_fit_evaluation", False) and "VisionLanguageModule" not in model_cfg["_target_"]:
             from src.utils.post_fit_evaluation import post_fit_evaluation   # :179-183
-            fold_metrics.update(post_fit_evaluation(model, fold_dm, trainer))
+            fold_metrics.update(post_fit_evaluation(model, fold_dm, trainer,
+                                                    tsne=bool(cfg.get("post_fit_tsne", False))))
         all_fold_metrics.append(fold_metrics)
         if not cfg.get("k_fold_cross_validation", False):
             break

@@ -4,18 +4,25 @@ plot_confusion_matrix.py:14-60): two silhouette scores of the image network's
 features (clusters = tumour label, clusters = source dataset) and the 2x2
 confusion matrix at a 0.5 threshold, for the validation and the train loaders.
 
-Only the numbers are computed: the t-SNE and the figures need W&B and are not
-built.  Each batch goes through the module once (features and logits come from
+On request (`tsne=True`, the config key `post_fit_tsne`) the 2-D t-SNE of the same
+features is computed as well (reference :62-66, sklearn's exact method restated in
+vlp_amd.metrics.tsne) and written per split as `tsne_{split}.npz` and, where
+matplotlib imports, as the reference's scatter `tsne_{split}.png`.  The W&B
+upload of the figures and the confusion-matrix figure are not built.
+
+Each batch goes through the module once (features and logits come from
 the same forward); the features stay on the device and the silhouette's distance
-sums run there (vlp_amd/metrics.py -> vlp_cluster_dist_sums), only the tumour
-labels and dataset names are host lists.  There are no collectives: under data
-parallelism every rank evaluates the loaders it is given.
+sums and the t-SNE run there (vlp_amd/metrics.py -> vlp_cluster_dist_sums,
+vlp_tsne_*), only the tumour labels and dataset names are host lists.  There are
+no collectives: under data parallelism every rank evaluates the loaders it is given.
 """
 from __future__ import annotations
 
 import logging
 import os
-from typing import Any, Dict
+from typing import Any, Dict, Optional
+
+import numpy as np
 
 import torch
 
@@ -54,8 +61,10 @@ def _features_and_logits(model, batch):
     return features, model.forward_head(features)
 
 
-def evaluate_split(model, dataloaders) -> Dict[str, Any]:
-    """Silhouette scores and confusion matrix of `model` over a loader or a list of loaders."""
+def evaluate_split(model, dataloaders, tsne: bool = False) -> Dict[str, Any]:
+    """Silhouette scores and confusion matrix of `model` over a loader or a list of loaders.
+    With `tsne` also "tsne" ([N, 2] CPU tensor), "tsne_kl" and the "tumor" / "dataset" lists
+    its rows follow (perplexity N - 1 below 30 samples, else 30: reference :62-65)."""
     if not isinstance(dataloaders, (list, tuple)):
         dataloaders = [dataloaders]
     was_training = model.training
@@ -84,14 +93,60 @@ def evaluate_split(model, dataloaders) -> Dict[str, Any]:
         by_dataset = float("nan")
     else:
         by_dataset = metrics.silhouette_score(x, dataset)
-    return {"silhouette_score_based_on_tumor": metrics.silhouette_score(x, tumor),
-            "silhouette_score_based_on_dataset": by_dataset,
-            "confusion_matrix": [[tn, fp], [fn, tp]]}
+    out = {"silhouette_score_based_on_tumor": metrics.silhouette_score(x, tumor),
+           "silhouette_score_based_on_dataset": by_dataset,
+           "confusion_matrix": [[tn, fp], [fn, tp]]}
+    if tsne:
+        emb, kl = metrics.tsne(x, perplexity=len(tumor) - 1 if len(tumor) < 30 else 30)
+        out.update({"tsne": emb.cpu(), "tsne_kl": kl, "tumor": tumor, "dataset": dataset})
+    return out
 
 
-def post_fit_evaluation(model, datamodule, trainer) -> Dict[str, Any]:
+_MARKERS = "oXs^vD"
+
+
+def save_tsne(res: Dict[str, Any], split: str, out_dir: str) -> None:
+    """tsne_{split}.npz (y, tumor, dataset) and, if matplotlib imports, tsne_{split}.png: the
+    embedding coloured by dataset, marker by tumour label, both silhouette scores in the corner."""
+    os.makedirs(out_dir, exist_ok=True)
+    y = res["tsne"].numpy()
+    tumor, dataset = np.asarray(res["tumor"]), np.asarray(res["dataset"])
+    np.savez(os.path.join(out_dir, f"tsne_{split}.npz"), y=y, tumor=tumor, dataset=dataset)
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        log.info("post_fit_evaluation: matplotlib is not installed; tsne_%s.png is not written", split)
+        return
+    fig, ax = plt.subplots(figsize=(10, 8))
+    colours = plt.get_cmap("tab10")
+    for di, name in enumerate(sorted(set(dataset.tolist()))):
+        for ti, t in enumerate(sorted(set(tumor.tolist()))):
+            sel = (dataset == name) & (tumor == t)
+            if sel.any():
+                ax.scatter(y[sel, 0], y[sel, 1], s=60, color=colours(di % 10), marker=_MARKERS[ti % len(_MARKERS)],
+                           edgecolors="white", linewidths=0.5, label=f"{name}, tumor {t}")
+    ax.set_xlabel("tsne-1")
+    ax.set_ylabel("tsne-2")
+    ax.set_title(f"{split}: t-SNE of features colored by Dataset (color) and Tumor (marker)")
+    ax.text(0.99, 0.01,
+            f"Silhouette Score Based on Tumor/No Tumor: {res['silhouette_score_based_on_tumor']:.4f}\n"
+            f"Silhouette Score Based on Dataset: {res['silhouette_score_based_on_dataset']:.4f}",
+            ha="right", va="bottom", transform=ax.transAxes, fontsize=12,
+            bbox=dict(facecolor="white", alpha=0.6, edgecolor="gray"))
+    ax.legend(bbox_to_anchor=(1.05, 1), loc="upper left")
+    fig.tight_layout()
+    fig.savefig(os.path.join(out_dir, f"tsne_{split}.png"), dpi=100)
+    plt.close(fig)
+
+
+def post_fit_evaluation(model, datamodule, trainer, tsne: bool = False,
+                        out_dir: Optional[str] = None) -> Dict[str, Any]:
     """Reload the best checkpoint and evaluate the validation and train loaders; the
-    reference's W&B keys, the confusion matrix as four counts per split."""
+    reference's W&B keys, the confusion matrix as four counts per split.  With `tsne`
+    also `tsne_kl_{split}`, and the embedding files of save_tsne in `out_dir` (default:
+    the directory of the best checkpoint)."""
     cb = best_checkpoint_callback(trainer)
     if cb is None:
         log.info("Train: No silhouette scores or confusion matrix, since no checkpoint callback monitoring a "
@@ -107,12 +162,15 @@ def post_fit_evaluation(model, datamodule, trainer) -> Dict[str, Any]:
     best = type(model).load_from_checkpoint(path, device=model.device)
     out: Dict[str, Any] = {}
     for split, loaders in (("validation", datamodule.val_dataloader()), ("train", datamodule.train_dataloader())):
-        res = evaluate_split(best, loaders)
+        res = evaluate_split(best, loaders, tsne=tsne)
         out[f"silhouette_score_based_on_tumor_{split}"] = res["silhouette_score_based_on_tumor"]
         out[f"silhouette_score_based_on_dataset_{split}"] = res["silhouette_score_based_on_dataset"]
         (tn, fp), (fn, tp) = res["confusion_matrix"]
         for k, v in (("tn", tn), ("fp", fp), ("fn", fn), ("tp", tp)):
             out[f"confusion_matrix_{split}/{k}"] = v
+        if tsne:
+            out[f"tsne_kl_{split}"] = res["tsne_kl"]
+            save_tsne(res, split, out_dir or os.path.dirname(path))
     for k, v in out.items():
         log.info("Train: %s = %s", k, v)
     return out

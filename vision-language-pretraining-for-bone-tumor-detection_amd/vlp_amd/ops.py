@@ -776,6 +776,57 @@ def cluster_dist_sums(x, labels_i32, C, xq=None):
     return out
 
 
+# ---------------- post-fit t-SNE ----------------
+TSNE_MAX_N = 32768   # kTsneMaxN of csrc/tsne_ops.hip: P [N, N] fp32 stays within 4 GB
+TSNE_PARTS = 7       # kParts: doubles per row of the all-pairs pass
+
+
+def tsne_sqdist(x):
+    """[N, N] fp32 squared Euclidean distances of the rows of x [N, D] (direct
+    differences: zero diagonal, symmetric bit for bit)."""
+    x = x.float().contiguous()
+    N, D = x.shape
+    d2 = torch.empty(N, N, dtype=torch.float32, device=x.device)
+    lib().vlp_tsne_sqdist(N, D, ptr(x), D, ptr(d2), N, _s())
+    return d2
+
+
+def tsne_affinities(d2, perplexity, return_conditional=False):
+    """sklearn's joint probabilities P [N, N] fp32 of the squared distances d2
+    [N, N] fp32 (vlp_tsne_affinities); with return_conditional also the
+    conditional matrix the bisection left, fp32."""
+    d2 = d2.float().contiguous()
+    N = d2.shape[0]
+    if d2.shape != (N, N):
+        raise ValueError(f"tsne_affinities: d2 must be square, got {tuple(d2.shape)}")
+    cond = torch.empty(N, N, dtype=torch.float32, device=d2.device)
+    P = torch.empty(N, N, dtype=torch.float32, device=d2.device)
+    ws = torch.empty(N + 1, dtype=torch.float64, device=d2.device)
+    lib().vlp_tsne_affinities(N, ptr(d2), N, float(perplexity), ptr(cond), ptr(ws), ptr(P), _s())
+    return (P, cond) if return_conditional else P
+
+
+def tsne_pairs(y, P, parts, check):
+    """parts [N, 7] fp64 <- the per-row sums of one iteration over y [N, 2], P [N, N]."""
+    N = y.shape[0]
+    assert y.shape == (N, 2) and P.shape == (N, N) and parts.shape == (N, TSNE_PARTS)
+    assert y.is_contiguous() and P.is_contiguous() and parts.is_contiguous()
+    assert y.dtype == P.dtype == torch.float32 and parts.dtype == torch.float64
+    lib().vlp_tsne_pairs(N, ptr(y), ptr(P), ptr(parts), int(bool(check)), _s())
+
+
+def tsne_update(parts, y, update, gains, exag, momentum, lr, check, stats):
+    """One gains + momentum step in place on y, update, gains [N, 2] fp32; when
+    check, stats [2] fp64 <- (KL, norm of the gained gradient)."""
+    N = y.shape[0]
+    for t in (y, update, gains):
+        assert t.shape == (N, 2) and t.dtype == torch.float32 and t.is_contiguous()
+    assert parts.shape == (N, TSNE_PARTS) and parts.dtype == torch.float64 and parts.is_contiguous()
+    assert stats.shape == (2,) and stats.dtype == torch.float64
+    lib().vlp_tsne_update(N, ptr(parts), ptr(y), ptr(update), ptr(gains), float(exag), float(momentum), float(lr),
+                          int(bool(check)), ptr(stats), _s())
+
+
 # ---------------- NesT image encoder (SURVEY §8(f) row 2) ----------------
 def nest_attn_fwd(qkv, out, lse, BT, H, N, scale):
     tk = ktimer.begin("nest_attn_fwd", 4.0 * BT * H * N * N * 32)
