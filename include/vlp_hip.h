@@ -449,6 +449,59 @@ int vlp_tsne_pairs(int N, const float* Y, const float* P, double* parts, int che
 int vlp_tsne_update(int N, const double* parts, float* Y, float* update, float* gains, float exag,
                     float momentum, float lr, int check, double* stats, void* stream);
 
+/* ---------------- the linear probe's logistic regression ----------------
+ * Replace sklearn.linear_model.LogisticRegression (and decision_function / predict) over the
+ * image features in LinearProbeCallback.py:72-85.  The objective is sklearn's binary L2 one with
+ * an unpenalised intercept, scaled as sklearn >= 1.4 scales it:
+ *   f(w, b) = (1/N) sum_i [softplus(z_i) - y_i z_i] + (lambda / 2) |w|^2,  z_i = x_i . w + b,
+ *   lambda = 1 / (C N),
+ * solved by a truncated Newton method (conjugate gradients on Hessian-vector products).  x [N][ldx]
+ * is fp32 as the encoders return it, y [N] holds 0.0 / 1.0, everything else is fp64: the
+ * coefficient vectors are D + 1 doubles (the intercept last; x~ = (x, 1) below).  No atomics, every
+ * sum in one fixed order: two fits agree bit for bit.  hipErrorInvalidValue before any launch:
+ * a NULL pointer that the call uses, N < 1, N > 2^30, D < 1, D > 2048, ldx < D, C <= 0 (or NaN),
+ * a mode outside 0 .. 3.
+ *
+ * vlp_logreg_pass: one pass over X; workgroup g owns rows [32 g, 32 g + 32) and writes
+ * parts[g][0 .. D + 2), with G = ceil(N / 32) partials in all.  With t_i = x~_i . u:
+ *   mode 0 GRAD   s[i] = p_i (1 - p_i) (written), c_i = p_i - y_i with p_i = sigmoid(t_i),
+ *                 l_i = softplus(t_i) - y_i t_i; parts[g] = { sum c_i x_i, sum c_i, sum l_i }
+ *   mode 1 HVP    c_i = s[i] t_i (s read); parts[g] = { sum c_i x_i, sum c_i, 0 }; returns at
+ *                 entry where state is non-NULL and its done flag is set
+ *   mode 2 LOSS   parts[g][D + 1] = sum l_i, the rest of parts untouched
+ *   mode 3 SCORES z[i] = t_i, nothing else (decision_function)
+ * sigmoid and softplus are the overflow-safe forms in e = exp(-|t|): softplus(750) = 750 exactly,
+ * p is exactly 1 from t = 37 up and exactly 0 once e^t underflows, s is exactly 0 there, and no
+ * inf or NaN arises from finite inputs.  Pointers a mode does not use may be NULL.
+ *
+ * The four kernels below run in one workgroup.  vec holds { g, d, r, q }, 4 (D + 1) doubles;
+ * state holds 10 doubles of which the host reads the first five, 40 bytes per outer iteration and
+ * the fit's only device-to-host traffic: [0] f(w), [1] |g|_inf, [2] g . d, [3] f(wt), [4] CG steps
+ * taken, [5] the penalty of wt, [6] r . r, [7] the CG tolerance, [8] the done flag, [9] |g|_2.
+ * `fold` is (parts[0][j] + parts[1][j] + ...) / N in ascending g; products are rounded on their
+ * own (no multiply-add), vector sums run thread-strided (entries t, t + 1024, t + 2048) and then
+ * through a halving tree over 1024 slots, so a numpy evaluation in that order gives the same bits.
+ *
+ * vlp_logreg_newton_begin (after a GRAD pass at w): g = fold + lambda (w, 0); [0] = fold of the
+ * losses + (lambda / 2) |w|^2; [1]; [9]; d = 0, r = q = -g; [2] = [4] = 0; [6] = g . g;
+ * [7] = min(0.5, sqrt |g|_2) |g|_2; [8] = 1 where |g|_inf <= tol or g = 0, else 0.
+ * vlp_logreg_cg_step (after an HVP pass at q): returns at entry where [8] is set.  Hq = fold +
+ * lambda (q, 0); alpha = [6] / q . Hq; d += alpha q; r -= alpha Hq; beta = r . r / [6]; q = r + beta q;
+ * [2] = g . d; [4] += 1; [6] = r . r; [8] = 1 where sqrt(r . r) <= [7].  A curvature q . Hq that is not
+ * positive (rounding only: the objective is strictly convex) sets [8] and changes nothing else.
+ * vlp_logreg_trial: wt = w + t d; [5] = (lambda / 2) |wt[0 .. D)|^2.
+ * vlp_logreg_trial_loss (after a LOSS pass at wt): [3] = fold of the losses + [5]. */
+int vlp_logreg_pass(int mode, int N, int D, const float* x, long long ldx, const double* y,
+                    const double* u, double* s, double* parts, double* z, const double* state,
+                    void* stream);
+int vlp_logreg_newton_begin(int N, int D, double C, const double* parts, const double* w, double tol,
+                            double* vec, double* state, void* stream);
+int vlp_logreg_cg_step(int N, int D, double C, const double* parts, double* vec, double* state,
+                       void* stream);
+int vlp_logreg_trial(int N, int D, double C, const double* w, double t, const double* vec, double* wt,
+                     double* state, void* stream);
+int vlp_logreg_trial_loss(int N, int D, const double* parts, double* state, void* stream);
+
 /* ---------------- NesT image encoder (BASELINE configs[3]) ----------------
  * Replace timm nest.py's pieces behind ImageEncoder's timm.create_model("nest_small", ...)
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,

@@ -26,6 +26,10 @@ numbers join the fold's metrics (src/utils/post_fit_evaluation.py).  With
 `post_fit_tsne: true` as well (absent = off, `..._mi355x_eval_tsne`) the evaluation
 also computes the reference's 2-D t-SNE of those features on the device, adds
 `tsne_kl_{split}` and writes `tsne_{split}.npz` / `.png` beside the best checkpoint.
+The pretraining linear probe (LinearProbeCallback, added when the run has
+`downstream_data`) takes the top-level key `linear_probe: {fit, every_n_epochs}`;
+`fit: device` fits and scores the probe on the GPU without sklearn, and
+`experiment=pretrain/pretrain_resnet34_tinybert_mi355x_probe` selects its checkpoint on it.
 Out of scope: W&B loggers (configured loggers whose package is
 absent are skipped with a warning), the confusion-matrix figure and
 downstream zero-shot evaluation.
@@ -151,7 +155,9 @@ def train(cfg: Dict[str, Any]) -> Tuple[Dict[str, Any], Dict[str, Any]]:
             from src.utils.LinearProbeCallback import LinearProbeCallback
             ds_dm = instantiate(cfg["downstream_data"])
             dm, _ = next(ds_dm.get_cv_splits())
-            callbacks.append(LinearProbeCallback(dm.train_dataloader(), dm.val_dataloader()))
+            # top-level `linear_probe: {fit: device, every_n_epochs: ...}`; absent = the reference's probe
+            callbacks.append(LinearProbeCallback(dm.train_dataloader(), dm.val_dataloader(),
+                                                 **dict(cfg.get("linear_probe") or {})))
             log.info("Train: Added LinearProbeCallback to callbacks.")
         log.info("Train: Instantiating trainer <%s>", cfg["trainer"]["_target_"])
         loggers = instantiate_loggers(cfg.get("logger"))

@@ -17,9 +17,15 @@ tensor from torch.cdist in fp64 (the off-GPU path).
 tsne restates sklearn.manifold.TSNE(method="exact", init="pca") (the reference
 calls it on the same features, plot_tsne_and_calculate_silhouette.py:62-66); see
 its docstring.
+
+logistic_regression, balanced_accuracy and binary_auroc are the pretraining
+linear probe (reference LinearProbeCallback.py:72-85: sklearn's
+LogisticRegression, balanced_accuracy_score and roc_auc_score) on the features'
+device; see their docstrings.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import List, Sequence, Tuple, Union
 
@@ -279,3 +285,230 @@ def tsne(x: torch.Tensor, perplexity: float = 30.0, max_iter: int = 1000, early_
     if it + 1 < max_iter:
         kl, it = descend(it + 1, max_iter, 1.0, 0.8, n_iter_without_progress)
     return run.y, kl
+
+
+# ---------------- the linear probe: logistic regression, balanced accuracy, AUROC ----------------
+LOGREG_MAX_D = 2048    # kLrMaxD of csrc/logreg_ops.hip
+_LOGREG_ROWS = 32      # kLrRows: rows per partial of the device passes
+_CG_BUDGET = 32        # HVP + cg_step pairs enqueued per outer iteration
+_ARMIJO_C1 = 1e-4
+_MIN_STEP = 2.0 ** -30
+
+
+def logreg_passes_cpu(x: torch.Tensor, y: torch.Tensor, u: torch.Tensor):
+    """The GRAD pass in torch fp64 at u [D + 1]: (sum of the losses, sum_i c_i (x_i, 1) [D + 1],
+    s [N]) with the overflow-safe forms of csrc/logreg_ops.hip (e = exp(-|t|))."""
+    t = x @ u[:-1] + u[-1]
+    e = torch.exp(-t.abs())
+    inv = 1.0 / (1.0 + e)
+    p = torch.where(t >= 0, inv, e * inv)
+    c = p - y
+    loss = (torch.where(y > 0.5, -t, t).clamp_min(0.0) + torch.log1p(e)).sum()
+    return loss, torch.cat([x.T @ c, c.sum()[None]]), e * inv * inv
+
+
+class _CpuNewton:
+    """One outer iteration of the truncated Newton method in torch fp64: the same
+    quantities in the same roles as the kernels of csrc/logreg_ops.hip."""
+
+    def __init__(self, x, y, C, tol):
+        self.x, self.y = x.double(), y.double()
+        self.N, self.D = x.shape
+        self.lam, self.tol = 1.0 / (C * self.N), tol
+        self.w = torch.zeros(self.D + 1, dtype=torch.float64)
+        self.nparts = 1
+
+    def _f(self, u):
+        loss, _, _ = logreg_passes_cpu(self.x, self.y, u)
+        return float(loss / self.N + 0.5 * self.lam * (u[:-1] ** 2).sum())
+
+    def _pen(self, v):   # lambda (v, 0)
+        return torch.cat([self.lam * v[:-1], torch.zeros(1, dtype=torch.float64)])
+
+    def iterate(self, budget):
+        loss, gs, s = logreg_passes_cpu(self.x, self.y, self.w)
+        g = gs / self.N + self._pen(self.w)
+        f = float(loss / self.N + 0.5 * self.lam * (self.w[:-1] ** 2).sum())
+        ginf, gn = float(g.abs().max()), float(g.norm())
+        d, r, q = torch.zeros_like(g), -g, -g.clone()
+        rs, cgtol, steps = float(g @ g), min(0.5, math.sqrt(gn)) * gn, 0
+        done = ginf <= self.tol or rs == 0.0
+        for _ in range(budget):
+            if done:
+                break
+            c = s * (self.x @ q[:-1] + q[-1])
+            hq = torch.cat([self.x.T @ c, c.sum()[None]]) / self.N + self._pen(q)
+            curv = float(q @ hq)
+            if not curv > 0.0:
+                break
+            alpha = rs / curv
+            d, r = d + alpha * q, r - alpha * hq
+            rs_new = float(r @ r)
+            q, rs, steps = r + (rs_new / rs) * q, rs_new, steps + 1
+            done = math.sqrt(rs) <= cgtol
+        self.d, self.status = d, [f, ginf, float(g @ d), float("nan"), float(steps)]
+        self.trial(1.0)
+
+    def trial(self, t):
+        self.wt = self.w + t * self.d
+        self.status[3] = self._f(self.wt)
+
+    def read(self):
+        return tuple(self.status)
+
+    def accept(self):
+        self.w = self.wt
+
+
+class _HipNewton:
+    def __init__(self, x, y, C, tol):
+        from . import ops
+        self.ops, self.x, self.y, self.C, self.tol = ops, x, y.double().contiguous(), C, tol
+        self.N, self.D = x.shape
+        self.nparts = ops.logreg_nparts(self.N)
+        z = functools.partial(torch.zeros, dtype=torch.float64, device=x.device)
+        self.w, self.wt, self.s = z(self.D + 1), z(self.D + 1), z(self.N)
+        self.parts, self.vec, self.state = z(self.nparts, self.D + 2), z(4, self.D + 1), z(ops.LOGREG_STATE)
+
+    def iterate(self, budget):
+        o, N, D = self.ops, self.N, self.D
+        o.logreg_pass(o.LOGREG_GRAD, self.x, self.y, self.w, s=self.s, parts=self.parts)
+        o.logreg_newton_begin(N, D, self.C, self.parts, self.w, self.tol, self.vec, self.state)
+        q = self.vec[3]
+        for _ in range(budget):   # the pairs past the done flag return at entry
+            o.logreg_pass(o.LOGREG_HVP, self.x, None, q, s=self.s, parts=self.parts, state=self.state)
+            o.logreg_cg_step(N, D, self.C, self.parts, self.vec, self.state)
+        self.trial(1.0)
+
+    def trial(self, t):
+        o = self.ops
+        o.logreg_trial(self.N, self.D, self.C, self.w, t, self.vec, self.wt, self.state)
+        o.logreg_pass(o.LOGREG_LOSS, self.x, self.y, self.wt, parts=self.parts)
+        o.logreg_trial_loss(self.N, self.D, self.parts, self.state)
+
+    def read(self):   # the fit's only device-to-host copy: 40 bytes per outer iteration
+        return tuple(self.state[:self.ops.LOGREG_STATUS].tolist())
+
+    def accept(self):
+        self.w, self.wt = self.wt, self.w
+
+
+class LogisticRegressionFit:
+    """What logistic_regression returns: coef_ [D] fp64 and intercept_ (0-d fp64) on the
+    features' device, n_iter_ (outer iterations taken), converged_ (the gradient's
+    largest entry was at most tol at coef_, intercept_)."""
+
+    def __init__(self, wb: torch.Tensor, n_iter: int, converged: bool, loss: float):
+        self._wb = wb
+        self.coef_, self.intercept_ = wb[:-1], wb[-1]
+        self.n_iter_, self.converged_, self.loss_ = n_iter, converged, loss
+
+    def decision_function(self, x: torch.Tensor) -> torch.Tensor:
+        """fp64 [M]: x_i . coef_ + intercept_ for the rows of x [M, D], on x's device."""
+        if x.dim() != 2 or x.shape[1] != self.coef_.shape[0]:
+            raise ValueError(f"decision_function: x must be [M, {self.coef_.shape[0]}], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            return x.double() @ self.coef_.to(x.device) + self.intercept_.to(x.device)
+        from . import ops
+        x = _logreg_features(x)
+        z = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+        if x.shape[0]:
+            ops.logreg_pass(ops.LOGREG_SCORES, x, None, self._wb.to(x.device), z=z)
+        return z
+
+    def predict(self, x: torch.Tensor) -> torch.Tensor:
+        """int64 [M]: class 1 where the score is > 0 (sklearn's rule), else 0."""
+        return (self.decision_function(x) > 0).long()
+
+
+def _logreg_features(x: torch.Tensor) -> torch.Tensor:
+    x = x.detach()
+    if x.dtype != torch.float32:
+        x = x.float()
+    return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+
+def logistic_regression(x: torch.Tensor, y: torch.Tensor, C: float = 1.0, max_iter: int = 100,
+                        tol: float = 1e-8) -> LogisticRegressionFit:
+    """sklearn's binary LogisticRegression(penalty="l2", C=C, fit_intercept=True) on x [N, D]
+    (taken as fp32, the encoders' output) and y [N] in {0, 1}: the minimiser of
+
+        f(w, b) = (1/N) sum_i [softplus(z_i) - y_i z_i] + |w|^2 / (2 C N),   z_i = x_i . w + b
+
+    (sklearn >= 1.4's scaling; the intercept is not penalised), by a truncated Newton method
+    in fp64 from w = 0: each outer iteration takes the direction d of at most _CG_BUDGET
+    conjugate-gradient steps on H d = -g (stopped at |r| <= min(0.5, sqrt|g|) |g|), tries
+    w + d, and halves the step while the Armijo test f(w + t d) <= f(w) + 1e-4 t g.d fails
+    (beyond the rounding of the two sums).  It stops when the largest entry of the gradient is
+    at most tol (converged_) or after max_iter outer iterations.  Unlike sklearn's L-BFGS,
+    whose tol=1e-4 ends the descent far from the optimum on separable features, the result does
+    not depend on the solver's path.
+
+    On a device tensor every pass over x and every vector update is a HIP kernel
+    (csrc/logreg_ops.hip), bitwise reproducible; the host reads 40 bytes per outer iteration,
+    after one 16-byte read of the two class counts before the first launch.  On a CPU tensor
+    the same driver runs on a torch-fp64 restatement of the passes.  ValueError, before any
+    launch: y with one class only (as sklearn) or with values outside {0, 1}."""
+    if x.dim() != 2 or y.dim() != 1 or y.shape[0] != x.shape[0]:
+        raise ValueError(f"logistic_regression: x [N, D] and y [N], got {tuple(x.shape)} and {tuple(y.shape)}")
+    N, D = x.shape
+    if N < 1 or not 1 <= D <= LOGREG_MAX_D:
+        raise ValueError(f"logistic_regression: N={N}, D={D}; at least one row and 1 to {LOGREG_MAX_D} columns")
+    if not C > 0 or not tol > 0 or max_iter < 1:
+        raise ValueError(f"logistic_regression: C={C}, tol={tol} must be positive and max_iter={max_iter} >= 1")
+    y = y.detach().to(x.device)
+    n1, n0 = torch.stack([(y == 1).sum(), (y == 0).sum()]).tolist()
+    if n0 + n1 != N:
+        raise ValueError("logistic_regression: the labels must be 0 or 1")
+    if n0 == 0 or n1 == 0:
+        raise ValueError("logistic_regression: the labels hold one class only, the fit needs both (as sklearn's)")
+    x = _logreg_features(x)
+    run = (_HipNewton if x.is_cuda else _CpuNewton)(x, y, float(C), float(tol))
+    # the two loss sums of the Armijo test each carry at most (rows per partial + partials + 8)
+    # roundings of relative size 2^-53: a difference below that is not a failed test
+    noise = 2.0 * (_LOGREG_ROWS + run.nparts + 8) * 2.0 ** -53
+    n_iter, converged, f = 0, False, float("nan")
+    for _ in range(max_iter):
+        run.iterate(_CG_BUDGET)
+        f, ginf, gd, ft, _ = run.read()
+        if ginf <= tol:
+            converged = True
+            break
+        t = 1.0
+        while not ft <= f + _ARMIJO_C1 * t * gd + noise * abs(f) and t > _MIN_STEP:
+            t *= 0.5
+            run.trial(t)
+            ft = run.read()[3]
+        run.accept()
+        n_iter, f = n_iter + 1, ft
+    return LogisticRegressionFit(run.w, n_iter, converged, f)
+
+
+def balanced_accuracy(y: torch.Tensor, pred: torch.Tensor) -> float:
+    """sklearn.metrics.balanced_accuracy_score for labels in {0, 1}: the mean of the two
+    recalls, counted on the tensors' device (one 8-byte read).  The recall of a class that y
+    lacks is 0, BinaryMetrics' zero-division rule, so a one-class y gives half the recall of
+    the class present (sklearn warns and averages over the classes present instead)."""
+    y, pred = y.reshape(-1), pred.reshape(-1).to(y.device)
+    pos, neg = y == 1, y == 0
+    n1, n0 = pos.sum().double(), neg.sum().double()
+    r1 = ((pred == 1) & pos).sum().double() / n1.clamp_min(1.0)
+    r0 = ((pred == 0) & neg).sum().double() / n0.clamp_min(1.0)
+    return float(0.5 * (r1 + r0))
+
+
+def binary_auroc(y: torch.Tensor, score: torch.Tensor) -> float:
+    """sklearn.metrics.roc_auc_score for labels in {0, 1}: the Mann-Whitney statistic with
+    tie-averaged ranks, (sum of the positives' ranks - n1 (n1 + 1) / 2) / (n1 n0), in fp64 on
+    the tensors' device (torch.sort is the only plumbing; one 8-byte read).  0.0 for a one-class
+    y, as BinaryMetrics (sklearn raises)."""
+    y, score = y.reshape(-1), score.reshape(-1).double().to(y.device)
+    pos = y == 1
+    n1, n0 = pos.sum().double(), (y == 0).sum().double()
+    vals, order = torch.sort(score)
+    _, inverse, counts = torch.unique_consecutive(vals, return_inverse=True, return_counts=True)
+    first = torch.cumsum(counts, 0) - counts                      # 0-based start of each tie group
+    ranks = (first.double() + 0.5 * (counts.double() + 1.0))[inverse]   # 1-based average rank
+    u = (ranks * pos[order].double()).sum() - n1 * (n1 + 1.0) / 2.0
+    auc = torch.where((n1 > 0) & (n0 > 0), u / (n1 * n0).clamp_min(1.0), torch.zeros_like(u))
+    return float(auc)

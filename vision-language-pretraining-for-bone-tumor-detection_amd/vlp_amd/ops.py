@@ -827,6 +827,66 @@ def tsne_update(parts, y, update, gains, exag, momentum, lr, check, stats):
                           int(bool(check)), ptr(stats), _s())
 
 
+# ---------------- the linear probe's logistic regression ----------------
+LOGREG_ROWS = 32      # kLrRows of csrc/logreg_ops.hip: rows of X per workgroup (one partial each)
+LOGREG_MAX_D = 2048   # kLrMaxD
+LOGREG_STATE = 10     # doubles of device state; the host reads the first LOGREG_STATUS of them
+LOGREG_STATUS = 5     # f, |g|_inf, g.d, f(trial), CG steps taken
+LOGREG_GRAD, LOGREG_HVP, LOGREG_LOSS, LOGREG_SCORES = 0, 1, 2, 3
+
+
+def logreg_nparts(N):
+    return (int(N) + LOGREG_ROWS - 1) // LOGREG_ROWS
+
+
+def logreg_pass(mode, x, y, u, s=None, parts=None, z=None, state=None):
+    """One pass of vlp_logreg_pass over x [N, D] fp32 (any row stride >= D, unit column stride)
+    at u [D + 1] fp64; y, s, z [N] fp64, parts [ceil(N / 32), D + 2] fp64, as the mode needs."""
+    N, D = x.shape
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and u.dtype == torch.float64 and u.shape == (D + 1,)
+    for t in (y, u, s, parts, z, state):
+        assert t is None or (t.dtype == torch.float64 and t.is_contiguous())
+    assert parts is None or parts.shape == (logreg_nparts(N), D + 2)
+    assert all(t is None or t.shape == (N,) for t in (y, s, z))
+    ldx = x.stride(0) if N > 1 else D
+    lib().vlp_logreg_pass(int(mode), N, D, ptr(x), ldx, ptr(y), ptr(u), ptr(s), ptr(parts), ptr(z), ptr(state),
+                          _s())
+
+
+def _logreg_vec_ok(D, vec, state):
+    assert vec.shape == (4, D + 1) and vec.dtype == torch.float64 and vec.is_contiguous()
+    assert state.shape == (LOGREG_STATE,) and state.dtype == torch.float64
+
+
+def logreg_newton_begin(N, D, C, parts, w, tol, vec, state):
+    """vec [4, D + 1] = (g, 0, -g, -g) and the state from the GRAD partials at w [D + 1]."""
+    _logreg_vec_ok(D, vec, state)
+    assert parts.shape == (logreg_nparts(N), D + 2) and parts.dtype == w.dtype == torch.float64
+    assert w.shape == (D + 1,) and parts.is_contiguous()
+    lib().vlp_logreg_newton_begin(N, D, float(C), ptr(parts), ptr(w), float(tol), ptr(vec), ptr(state), _s())
+
+
+def logreg_cg_step(N, D, C, parts, vec, state):
+    """One conjugate-gradient update of vec (d, r, q) from the HVP partials at q."""
+    _logreg_vec_ok(D, vec, state)
+    assert parts.shape == (logreg_nparts(N), D + 2) and parts.dtype == torch.float64 and parts.is_contiguous()
+    lib().vlp_logreg_cg_step(N, D, float(C), ptr(parts), ptr(vec), ptr(state), _s())
+
+
+def logreg_trial(N, D, C, w, t, vec, wt, state):
+    """wt [D + 1] = w + t d, and its penalty into the state."""
+    _logreg_vec_ok(D, vec, state)
+    assert w.shape == wt.shape == (D + 1,) and w.dtype == wt.dtype == torch.float64
+    lib().vlp_logreg_trial(N, D, float(C), ptr(w), float(t), ptr(vec), ptr(wt), ptr(state), _s())
+
+
+def logreg_trial_loss(N, D, parts, state):
+    """state[3] = f(wt) from the LOSS partials at wt."""
+    assert parts.shape == (logreg_nparts(N), D + 2) and parts.dtype == torch.float64 and parts.is_contiguous()
+    assert state.shape == (LOGREG_STATE,) and state.dtype == torch.float64
+    lib().vlp_logreg_trial_loss(N, D, ptr(parts), ptr(state), _s())
+
+
 # ---------------- NesT image encoder (SURVEY §8(f) row 2) ----------------
 def nest_attn_fwd(qkv, out, lse, BT, H, N, scale):
     tk = ktimer.begin("nest_attn_fwd", 4.0 * BT * H * N * N * 32)
