@@ -502,6 +502,37 @@ int vlp_logreg_trial(int N, int D, double C, const double* w, double t, const do
                      double* state, void* stream);
 int vlp_logreg_trial_loss(int N, int D, const double* parts, double* state, void* stream);
 
+/* ---------------- the baselines' binary classification metrics ----------------
+ * Replace torchmetrics' Binary{Accuracy, Precision, Recall, F1Score, AUROC} (threshold 0.5) of
+ * FusionModule.py:251-286 / :393-504 and OnlyImagingModule.py:305-430 with an integer
+ * accumulator on the device.  The device
+ * compares fp32 scores and adds integers, nothing else: no sum depends on its order, and the host
+ * derives the five values from six integers.  No atomics; the calls of one accumulator belong on
+ * one stream.  hipErrorInvalidValue before any launch: a NULL pointer that the call uses, a
+ * negative size, a label_kind outside 0 .. 2, offset + n > capacity, n > 2^18 or splits outside
+ * 1 .. ceil(n / 256) for the pair count.
+ *
+ * vlp_binmetric_append (one workgroup): scores[offset + i] = prob[i] and labels[offset + i] = the
+ * label of row i for i < n -- 1 where the input is 1, 0 where it is 0, else 2, which is counted
+ * nowhere -- and counts[0 .. 4) += the batch's tp, fp, fn, tn with the prediction prob >= 0.5f.
+ * label_kind: 0 int64, 1 int32, 2 uint8 (bool).  prob is the probability, not the logit.  n = 0
+ * returns without a launch.
+ * vlp_binmetric_pairs: over i with labels[i] = 1 and j with labels[j] = 0 among the first n rows,
+ * wins = #{scores[i] > scores[j]} and ties = #{scores[i] == scores[j]}, so that
+ * AUROC = (2 wins + ties) / (2 n1 n0), the Mann-Whitney statistic with tie-averaged ranks.  Grid
+ * (ceil(n / 256), splits): a workgroup keeps 256 values of i in registers and streams its share of
+ * the j range through LDS; parts[(by * ceil(n / 256) + bx)][2] = its { wins, ties }.  O(n^2) pairs:
+ * meant for n <= 2^18.  A NaN score is out of contract (it is counted in no pair).
+ * vlp_binmetric_fold (one workgroup): out[0 .. 4) = counts, out[4] = sum of parts[.][0], out[5] =
+ * sum of parts[.][1]: the 48 bytes the host reads.  nparts = 0 gives zero pair counts. */
+int vlp_binmetric_append(int n, const float* prob, const void* label, int label_kind, float* scores,
+                         unsigned char* labels, long long offset, long long capacity, long long* counts,
+                         void* stream);
+int vlp_binmetric_pairs(int n, const float* scores, const unsigned char* labels, int splits,
+                        unsigned long long* parts, void* stream);
+int vlp_binmetric_fold(int nparts, const unsigned long long* parts, const long long* counts, long long* out,
+                       void* stream);
+
 /* ---------------- NesT image encoder (BASELINE configs[3]) ----------------
  * Replace timm nest.py's pieces behind ImageEncoder's timm.create_model("nest_small", ...)
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,

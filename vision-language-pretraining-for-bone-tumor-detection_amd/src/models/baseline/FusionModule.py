@@ -8,7 +8,15 @@ state-dict keys (tabular_network.*, image_network.<timm resnet34 incl. fc>,
 combination_network.*), same forward(x, age, sex, anatomy_site) -> (logits,
 image_features) (:318-326), _compute_loss (:341-390: weighted BCE + optional
 CORAL), configure_optimizers (:127-201: image_backbone / head_and_remaining
-groups), training_step (:392-420) and validation_step's dataloader index rule.
+groups), training_step (:392-420), validation_step's dataloader index rule
+(:423-468) and on_validation_epoch_end's combined evaluation over the cached
+probabilities, logits and image features (:470-504).
+
+Metrics: the reference's torchmetrics Binary{Accuracy, Precision, Recall, F1Score,
+AUROC} under train/, val/internal/, val/btxrd/ and val/combined/ are
+vlp_amd.metrics.BinaryMetricsDevice accumulators: the epoch's probabilities and
+labels stay on the device (one launch per step, no device-to-host copy) and each
+set of five values costs one 48-byte read at the end of the epoch.
 
 The image network is the HIP ResNet34 tower of the pretraining path
 (vlp_amd/resnet34.py, every conv / BN / pool on the hand-written kernels, >99.9 %
@@ -20,7 +28,7 @@ fc, the 15->32->20->10 tabular MLP with BatchNorm1d, the 20->1 combination and
 the loss (a few kFLOP per sample) run as device tensor ops.
 
 Not built: the vit / resnet50 / nest_small / torchxrayvision backbones
-(NotImplementedError), torchmetrics accuracy/AUROC logging.  The t-SNE of the image features is part
+(NotImplementedError).  The t-SNE of the image features is part
 of the post-fit evaluation (src/utils/post_fit_evaluation.py, `post_fit_tsne`).
 Pretrained VLP checkpoints load with torch.load(weights_only=True) (the
 reference uses weights_only=False, :84).
@@ -43,6 +51,7 @@ if _PKG not in sys.path:
 from src.models.pretrain.VisionLanguageModule import (VisionLanguageModule, _Base, _HAVE_LIGHTNING,  # noqa: E402
                                                        _default_device)
 from src.utils.coral_loss.coral import coral  # noqa: E402
+from vlp_amd.metrics import BinaryMetricsDevice  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
 
 logger = logging.getLogger("project")
@@ -120,11 +129,18 @@ class FusionModule(_Base):
                         used, pretrained_vlp_module, len(missing))
         self.combination_network = nn.Linear(20, 1).to(dev)                            # :117
         self.label_weights = torch.Tensor(label_weights)                               # :119
+        self.train_metrics = BinaryMetricsDevice()                                     # :251-286
+        self.val_metrics = {k: BinaryMetricsDevice() for k in ("internal", "btxrd", "combined")}
+        self._clear_val_cache()
         logger.info("FusionModule (MI355X): initialized %s, compute_dtype=%s", model, compute_dtype)
 
     @property
     def device(self):
         return self.combination_network.weight.device
+
+    def _clear_val_cache(self):
+        self.all_val_probs, self.all_val_labels, self.all_val_logits = [], [], []
+        self.all_val_image_features, self.all_val_datset_labels = [], []
 
     def all_reduce_gradients(self, world: int) -> None:
         """Data-parallel gradient mean (DDP semantics, called by the trainer after
@@ -218,17 +234,23 @@ class FusionModule(_Base):
         return (x, batch["tumor"], batch["dataset"], batch["anatomy_site_encoded"], batch["age_encoded"],
                 batch["sex_encoded"])
 
-    def training_step(self, batch, batch_idx=None):
+    def training_step(self, batch, batch_idx=None):                                  # :393-421
         x, labels, dataset, site, age, sex = self._unpack(batch)
         logits, image_features = self.forward(x, age, sex, site)
         loss, cls, cor = self._compute_loss(image_features, logits, labels, dataset)
+        self.train_metrics.update(torch.sigmoid(logits), labels)
         bs = x.shape[0]
         self.log("train/classification_loss", cls, on_step=True, on_epoch=True, batch_size=bs)
         self.log("train/coral_loss", cor, on_step=True, on_epoch=True, batch_size=bs)
         self.log("train/loss", loss, on_step=True, on_epoch=True, batch_size=bs)
         return loss
 
-    def validation_step(self, batch, batch_idx, dataloader_idx=0):
+    def on_train_epoch_end(self):
+        for k, v in self.train_metrics.compute().items():
+            self.log(f"train/{k}", v, on_step=False, on_epoch=True)
+        self.train_metrics.reset()
+
+    def validation_step(self, batch, batch_idx, dataloader_idx=0):                   # :423-468
         x, labels, dataset, site, age, sex = self._unpack(batch)
         logits, image_features = self.forward(x, age, sex, site)
         loss, _, _ = self._compute_loss(image_features, logits, labels, dataset)
@@ -238,6 +260,37 @@ class FusionModule(_Base):
             key = "btxrd"
         else:
             raise ValueError(f"FusionModule: Validation dataloader index {dataloader_idx} is not supported.")
+        probs = torch.sigmoid(logits.detach())
+        self.all_val_probs.append(probs)
+        self.all_val_labels.append(labels.to(probs.device))
+        self.all_val_logits.append(logits.detach())
+        self.all_val_image_features.append(image_features.detach())
+        self.all_val_datset_labels.extend(dataset)
+        self.val_metrics[key].update(probs, labels)
         self.log(f"val/{key}/loss", loss, on_step=False, on_epoch=True, batch_size=x.shape[0],
                  add_dataloader_idx=False)
         return loss
+
+    @torch.no_grad()
+    def on_validation_epoch_end(self):                                               # :470-504
+        for key in ("internal", "btxrd"):
+            for k, v in self.val_metrics[key].compute().items():
+                self.log(f"val/{key}/{k}", v, on_step=False, on_epoch=True, add_dataloader_idx=False)
+            self.val_metrics[key].reset()
+        if not self.all_val_probs:
+            return
+        probs, labels = torch.cat(self.all_val_probs), torch.cat(self.all_val_labels)
+        logits, features = torch.cat(self.all_val_logits), torch.cat(self.all_val_image_features)
+        loss, cls, cor = self._compute_loss(features, logits, labels, self.all_val_datset_labels)
+        bs = features.shape[0]
+        self.log("val/combined/loss", loss, on_step=False, on_epoch=True, add_dataloader_idx=False, batch_size=bs)
+        self.log("val/combined/classification_loss", cls, on_step=False, on_epoch=True,
+                 add_dataloader_idx=False, batch_size=bs)
+        self.log("val/combined/coral_loss", cor, on_step=False, on_epoch=True, add_dataloader_idx=False,
+                 batch_size=bs)
+        combined = self.val_metrics["combined"]
+        combined.update(probs, labels)
+        for k, v in combined.compute().items():
+            self.log(f"val/combined/{k}", v, on_step=False, on_epoch=True, add_dataloader_idx=False, batch_size=bs)
+        combined.reset()
+        self._clear_val_cache()

@@ -30,7 +30,12 @@ weights_only=False, :76).
 
 Metrics: torchmetrics is absent from this image; `BinaryMetrics` restates the
 Binary{Accuracy,Precision,Recall,F1Score,AUROC} values at threshold 0.5 that the
-reference logs (AUROC as the Mann-Whitney rank statistic with tie averaging).
+reference logs (AUROC as the Mann-Whitney rank statistic with tie averaging) on the
+host.  With `metrics_on_device=True` the four accumulators are
+vlp_amd.metrics.BinaryMetricsDevice instead: the epoch's probabilities and labels
+stay on the device, a step adds one launch and no device-to-host copy, and each
+set of five values costs one 48-byte read at the end of the epoch; both return
+the same bits (the shared binary_metrics_from_counts).
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ if _PKG not in sys.path:
 from src.models.baseline.FusionModule import FusionModule, ResNet34Classifier  # noqa: E402
 from src.models.pretrain.VisionLanguageModule import (VisionLanguageModule, _Base, _HAVE_LIGHTNING,  # noqa: E402
                                                        _default_device)
+from vlp_amd.metrics import BinaryMetricsDevice, binary_metrics_from_counts  # noqa: E402
 from vlp_amd.nest import NestTower  # noqa: E402
 
 logger = logging.getLogger("project")
@@ -108,11 +114,9 @@ def binary_metrics(p: torch.Tensor, y: torch.Tensor):
     tp = int(((pred == 1) & (y == 1)).sum())
     fp = int(((pred == 1) & (y == 0)).sum())
     fn = int(((pred == 0) & (y == 1)).sum())
-    acc = int((pred == y).sum()) / y.numel() if y.numel() else 0.0
-    prec = tp / (tp + fp) if tp + fp else 0.0
-    rec = tp / (tp + fn) if tp + fn else 0.0
-    f1 = 2 * prec * rec / (prec + rec) if prec + rec else 0.0
-    npos, nneg = int((y == 1).sum()), int((y == 0).sum())
+    tn = int(((pred == 0) & (y == 0)).sum())
+    npos, nneg = tp + fn, fp + tn
+    u2 = 0
     if npos and nneg:
         # Mann-Whitney U with average ranks for ties = the area under the ROC curve
         order = torch.argsort(p.double())
@@ -127,10 +131,8 @@ def binary_metrics(p: torch.Tensor, y: torch.Tensor):
             i = j + 1
         r = torch.empty_like(ranks)
         r[order] = ranks
-        auroc = float((r[y == 1].sum() - npos * (npos + 1) / 2) / (npos * nneg))
-    else:
-        auroc = 0.0
-    return {"accuracy": acc, "precision": prec, "recall": rec, "f1": f1, "auroc": auroc}
+        u2 = 2.0 * float(r[y == 1].sum() - npos * (npos + 1) / 2)   # ranks are half-integers: exact
+    return binary_metrics_from_counts(tp, fp, fn, tn, u2)
 
 
 class OnlyImagingModule(_Base):
@@ -145,12 +147,14 @@ class OnlyImagingModule(_Base):
         compute_dtype: str = "fp32",
         image_size: int = 224,
         device=None,
+        metrics_on_device: bool = False,
         **kwargs,
     ):
         super().__init__()
         hp = dict(model=model, optimizer=optimizer, scheduler=scheduler, label_weights=label_weights,
                   coral_lambda=coral_lambda, pretrained_vlp_module=pretrained_vlp_module,
-                  compute_dtype=compute_dtype, image_size=image_size, **kwargs)
+                  compute_dtype=compute_dtype, image_size=image_size, metrics_on_device=metrics_on_device,
+                  **kwargs)
         if _HAVE_LIGHTNING:  # pragma: no cover
             self.save_hyperparameters(logger=False)
         else:
@@ -179,8 +183,9 @@ class OnlyImagingModule(_Base):
             logger.info("OnlyImagingModule: loaded %d pretrained vision-encoder parameters from %s "
                         "(%d missing keys: the classification head)", used, pretrained_vlp_module, len(missing))
         self.label_weights = torch.Tensor(label_weights)                               # :101
-        self.train_metrics = BinaryMetrics()
-        self.val_metrics = {"internal": BinaryMetrics(), "btxrd": BinaryMetrics(), "combined": BinaryMetrics()}
+        metric = BinaryMetricsDevice if metrics_on_device else BinaryMetrics
+        self.train_metrics = metric()
+        self.val_metrics = {"internal": metric(), "btxrd": metric(), "combined": metric()}
         self._clear_val_cache()
         logger.info("OnlyImagingModule (MI355X): initialized %s, compute_dtype=%s", model, compute_dtype)
 
@@ -308,6 +313,13 @@ class OnlyImagingModule(_Base):
                  add_dataloader_idx=False, batch_size=bs)
         self.log("val/combined/coral_loss", cor, on_step=False, on_epoch=True, add_dataloader_idx=False,
                  batch_size=bs)
-        for k, v in binary_metrics(probs.float().cpu(), labels.cpu().long()).items():
+        if self.hparams.metrics_on_device:
+            combined = self.val_metrics["combined"]
+            combined.update(probs, labels)
+            values = combined.compute()
+            combined.reset()
+        else:
+            values = binary_metrics(probs.float().cpu(), labels.cpu().long())
+        for k, v in values.items():
             self.log(f"val/combined/{k}", v, on_step=False, on_epoch=True, add_dataloader_idx=False, batch_size=bs)
         self._clear_val_cache()

@@ -22,6 +22,11 @@ logistic_regression, balanced_accuracy and binary_auroc are the pretraining
 linear probe (reference LinearProbeCallback.py:72-85: sklearn's
 LogisticRegression, balanced_accuracy_score and roc_auc_score) on the features'
 device; see their docstrings.
+
+BinaryMetricsDevice is the baselines' epoch accumulator for accuracy, precision,
+recall, F1 and AUROC with its state on the device (csrc/binmetric_ops.hip: integer
+counts, one 48-byte read per compute()); binary_metrics_from_counts is the host
+arithmetic it shares with OnlyImagingModule's binary_metrics.
 """
 from __future__ import annotations
 
@@ -512,3 +517,137 @@ def binary_auroc(y: torch.Tensor, score: torch.Tensor) -> float:
     u = (ranks * pos[order].double()).sum() - n1 * (n1 + 1.0) / 2.0
     auc = torch.where((n1 > 0) & (n0 > 0), u / (n1 * n0).clamp_min(1.0), torch.zeros_like(u))
     return float(auc)
+
+
+# ---------------- the baselines' binary classification metrics ----------------
+BINMETRIC_MAX_N = 1 << 18   # kBmMaxN of csrc/binmetric_ops.hip: the ceiling of the O(n^2) pair count
+
+
+def binary_metrics_from_counts(tp, fp, fn, tn, u2):
+    """The five values of torchmetrics' Binary{Accuracy, Precision, Recall, F1Score, AUROC} from the
+    confusion counts and u2 = 2 #{s_i > s_j} + #{s_i == s_j} over the pairs (positive i, negative
+    j), twice the Mann-Whitney statistic with tie-averaged ranks: AUROC = u2 / (2 n1 n0).
+    Precision, recall and F1 are 0.0 on a zero denominator (torchmetrics' zero_division default),
+    the AUROC is 0.0 when a class is absent.  Every quotient is one fp64 division of exact
+    integers (u2 may come as a float that holds an integer), so two callers that counted the same
+    samples return the same bits."""
+    n = tp + fp + fn + tn
+    acc = (tp + tn) / n if n else 0.0
+    prec = tp / (tp + fp) if tp + fp else 0.0
+    rec = tp / (tp + fn) if tp + fn else 0.0
+    f1 = 2 * prec * rec / (prec + rec) if prec + rec else 0.0
+    npos, nneg = tp + fn, fp + tn
+    auroc = float(u2 / (2 * npos * nneg)) if npos and nneg else 0.0
+    return {"accuracy": acc, "precision": prec, "recall": rec, "f1": f1, "auroc": auroc}
+
+
+def binary_pair_counts_cpu(scores: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int]:
+    """(wins, ties) of csrc/binmetric_ops.hip's pair count in plain torch: over i with
+    labels[i] == 1 and j with labels[j] == 0, #{scores[i] > scores[j]} and
+    #{scores[i] == scores[j]}, in row chunks of the positives."""
+    pos, neg = scores[labels == 1], scores[labels == 0]
+    wins = ties = 0
+    rows = max(1, (1 << 22) // max(1, neg.numel()))
+    for r in range(0, pos.numel(), rows):
+        p = pos[r:r + rows, None]
+        wins += int((p > neg[None, :]).sum())
+        ties += int((p == neg[None, :]).sum())
+    return wins, ties
+
+
+class BinaryMetricsDevice:
+    """BinaryMetrics (src/models/baseline/OnlyImagingModule.py) with its state on the scores'
+    device: reset(), update(probs, labels), compute() -> the same five keys, {} when empty.
+
+    The scores (fp32) and labels (uint8) of an epoch sit in two buffers that double through torch
+    when full; the host knows the fill count from the batch sizes.  update() is one launch
+    (vlp_binmetric_append) that also adds the batch's tp, fp, fn, tn at probs >= 0.5 into an
+    int64[4]; nothing is read back.  compute() counts the AUROC's pairs without a sort
+    (vlp_binmetric_pairs, O(n^2) comparisons, meant for n <= 2^18 = BINMETRIC_MAX_N; beyond it the
+    AUROC comes from binary_auroc on the device), folds, and reads 48 bytes -- tp, fp, fn, tn,
+    wins, ties -- the accumulator's only device-to-host copy; binary_metrics_from_counts finishes
+    on the host, as it does for binary_metrics, so the two paths return the same bits.  The device
+    does no floating-point arithmetic.  reset() zeroes the counters and the fill count and
+    allocates nothing.
+
+    Labels are 0 or 1 (int64, int32, uint8 or bool; any other value is counted in no cell and no
+    pair).  Scores are probabilities (sigmoid outputs), hence finite: a NaN is out of contract.
+    On CPU tensors the same integer counts come from plain torch (binary_pair_counts_cpu)."""
+
+    def __init__(self, capacity: int = 4096):
+        self._capacity = max(1, int(capacity))
+        self._scores = self._labels = self._counts = None
+        self._n = 0
+
+    def __len__(self):
+        return self._n
+
+    def reset(self):
+        self._n = 0
+        if self._counts is not None:
+            self._counts.zero_()
+
+    def _reserve(self, need: int, device: torch.device):
+        if self._scores is not None and self._scores.device != device:
+            if self._n:
+                raise ValueError(f"BinaryMetricsDevice: update on {device} after rows on {self._scores.device}")
+            self._scores = None
+        if self._scores is None:
+            cap = max(self._capacity, need)
+            self._scores = torch.empty(cap, dtype=torch.float32, device=device)
+            self._labels = torch.empty(cap, dtype=torch.uint8, device=device)
+            self._counts = torch.zeros(4, dtype=torch.int64, device=device)
+        elif need > self._scores.numel():
+            cap = max(2 * self._scores.numel(), need)
+            for name in ("_scores", "_labels"):
+                old = getattr(self, name)
+                new = torch.empty(cap, dtype=old.dtype, device=device)
+                new[:self._n].copy_(old[:self._n])
+                setattr(self, name, new)
+
+    def update(self, probs: torch.Tensor, labels: torch.Tensor):
+        p = probs.detach().reshape(-1)
+        if p.dtype != torch.float32:
+            p = p.float()
+        y = labels.detach().reshape(-1).to(p.device, non_blocking=True)
+        if y.dtype not in (torch.int64, torch.int32, torch.uint8, torch.bool):
+            y = y.long()
+        n = p.numel()
+        if y.numel() != n:
+            raise ValueError(f"BinaryMetricsDevice: {n} probabilities but {y.numel()} labels")
+        if n == 0:
+            return
+        self._reserve(self._n + n, p.device)
+        if p.is_cuda:
+            from . import ops
+            ops.binmetric_append(p.contiguous(), y.contiguous(), self._scores, self._labels, self._n, self._counts)
+        else:
+            y8 = torch.where(y == 1, 1, torch.where(y == 0, 0, 2)).to(torch.uint8)
+            self._scores[self._n:self._n + n] = p
+            self._labels[self._n:self._n + n] = y8
+            pred = p >= 0.5
+            self._counts += torch.stack([(pred & (y8 == 1)).sum(), (pred & (y8 == 0)).sum(),
+                                         (~pred & (y8 == 1)).sum(), (~pred & (y8 == 0)).sum()])
+        self._n += n
+
+    def counts(self) -> List[int]:
+        """[tp, fp, fn, tn, wins, ties] over the rows held (one 48-byte read on the device)."""
+        n = self._n
+        if n == 0:
+            return [0] * 6
+        s, y = self._scores[:n], self._labels[:n]
+        if not s.is_cuda:
+            return self._counts.tolist() + list(binary_pair_counts_cpu(s, y))
+        from . import ops
+        return ops.binmetric_counts(n, self._scores, self._labels, self._counts).tolist()
+
+    def compute(self) -> dict:
+        n = self._n
+        if n == 0:
+            return {}
+        if self._scores.is_cuda and n > BINMETRIC_MAX_N:   # past the pair count's ceiling: the sort-based AUROC
+            out = binary_metrics_from_counts(*self._counts.tolist(), 0)
+            out["auroc"] = binary_auroc(self._labels[:n], self._scores[:n])
+            return out
+        tp, fp, fn, tn, wins, ties = self.counts()
+        return binary_metrics_from_counts(tp, fp, fn, tn, 2 * wins + ties)

@@ -887,6 +887,59 @@ def logreg_trial_loss(N, D, parts, state):
     lib().vlp_logreg_trial_loss(N, D, ptr(parts), ptr(state), _s())
 
 
+# ---------------- the baselines' binary classification metrics ----------------
+BINMETRIC_TILE = 256         # kBmThreads = kBmTile of csrc/binmetric_ops.hip: the i tile and the j tile
+BINMETRIC_MAX_N = 1 << 18    # kBmMaxN: the ceiling of the O(n^2) pair count
+BINMETRIC_BLOCKS = 1024      # workgroups the pair count aims for (four per CU) when it splits the j range
+_BINMETRIC_KIND = {torch.int64: 0, torch.int32: 1, torch.uint8: 2}
+
+
+def binmetric_append(prob, label, scores, labels, offset, counts):
+    """scores[offset : offset + n] = prob, labels[offset : offset + n] = label as 0 / 1 (2 for any
+    other value) and counts [4] int64 += the batch's tp, fp, fn, tn at prob >= 0.5
+    (vlp_binmetric_append: one launch, nothing read back).  prob [n] fp32; label [n] int64, int32,
+    uint8 or bool."""
+    n = prob.numel()
+    if label.dtype == torch.bool:
+        label = label.view(torch.uint8)
+    if label.dtype not in _BINMETRIC_KIND:
+        raise TypeError(f"binmetric_append: labels must be int64, int32, uint8 or bool, got {label.dtype}")
+    assert prob.dtype == torch.float32 and prob.is_contiguous() and label.is_contiguous() and label.numel() == n
+    assert scores.dtype == torch.float32 and labels.dtype == torch.uint8 and scores.numel() == labels.numel()
+    assert scores.is_contiguous() and labels.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.shape == (4,)
+    if not 0 <= offset <= scores.numel() - n:
+        raise ValueError(f"binmetric_append: rows [{offset}, {offset + n}) do not fit {scores.numel()} slots")
+    lib().vlp_binmetric_append(n, ptr(prob), ptr(label), _BINMETRIC_KIND[label.dtype], ptr(scores), ptr(labels),
+                               int(offset), scores.numel(), ptr(counts), _s())
+
+
+def binmetric_grid(n):
+    """(workgroups along i, splits of the j range) of the pair count over n rows: the j range is
+    split until about BINMETRIC_BLOCKS workgroups run, one tile of j at the least per split."""
+    bx = (int(n) + BINMETRIC_TILE - 1) // BINMETRIC_TILE
+    return bx, max(1, min(bx, (BINMETRIC_BLOCKS + bx - 1) // bx))
+
+
+def binmetric_counts(n, scores, labels, counts):
+    """int64 [6] on the device: tp, fp, fn, tn (counts) and the pair counts wins, ties over the first
+    n rows of scores / labels (vlp_binmetric_pairs + vlp_binmetric_fold).  n <= BINMETRIC_MAX_N."""
+    if not 0 <= n <= min(BINMETRIC_MAX_N, scores.numel()):
+        raise ValueError(f"binmetric_counts: n={n}; the pair count takes 0 to "
+                         f"{min(BINMETRIC_MAX_N, scores.numel())} rows")
+    assert scores.dtype == torch.float32 and labels.dtype == torch.uint8 and scores.numel() == labels.numel()
+    assert counts.dtype == torch.int64 and counts.shape == (4,)
+    out = torch.empty(6, dtype=torch.int64, device=scores.device)
+    parts, nparts = None, 0
+    if n:
+        bx, splits = binmetric_grid(n)
+        nparts = bx * splits
+        parts = torch.empty(nparts, 2, dtype=torch.int64, device=scores.device)
+        lib().vlp_binmetric_pairs(n, ptr(scores), ptr(labels), splits, ptr(parts), _s())
+    lib().vlp_binmetric_fold(nparts, ptr(parts), ptr(counts), ptr(out), _s())
+    return out
+
+
 # ---------------- NesT image encoder (SURVEY §8(f) row 2) ----------------
 def nest_attn_fwd(qkv, out, lse, BT, H, N, scale):
     tk = ktimer.begin("nest_attn_fwd", 4.0 * BT * H * N * N * 32)
