@@ -1006,11 +1006,10 @@ VLP_EXPORT int vlp_linear_wgrad_ws(int dtype, int M, int Nout, int Kin, const vo
   // each split reduces >= VLP_LINW_WS_ROWS token rows: the text tower runs on a
   // side stream beside the image tower, where CU time per FLOP (prologue,
   // epilogue, slab traffic), not latency, is what the step pays for
-  int ks = linw_splits(M, Nout, Kin);   // >= 256 token rows per split
-  while (ks > 1 && (long long)ks * Nout * Kin > ws_elems) --ks;
-  int kc = (M + ks - 1) / ks;
-  kc = (kc + 63) / 64 * 64;
-  ks = (M + kc - 1) / kc;
+  // the split may write the slabs that fit (at least one: a smaller workspace is an error)
+  const SlabPlan sp = plan_slabs(ws_elems, (long long)Nout * Kin, M);
+  if (sp.max_ks < 1) return (int)hipErrorInvalidValue;
+  int ks = 0;   // the count launched with
   MNMat<bf16> la{(const bf16*)dy, lddy, Nout, M};
   MNMat<bf16> lb{(const bf16*)x, ldx, Kin, M};
   EpiSplitStore ep{nullptr, nullptr, ws, Kin, (size_t)Nout * Kin};
@@ -1018,18 +1017,17 @@ VLP_EXPORT int vlp_linear_wgrad_ws(int dtype, int M, int Nout, int Kin, const vo
   if (linw_use_pp(M, Nout, Kin)) {
     // deep token reductions (NesT level 2) on the 256x256 ping-pong kernel: one
     // round of 256 workgroups, >= 2048 tokens per split, within the workspace
-    int k2 = linw_splits_pp(M, Nout, Kin);
-    while (k2 > 1 && (long long)k2 * Nout * Kin > ws_elems) --k2;
-    r = launch_gemm_pp<256, 256, 2, 4>(Nout, Kin, M, k2, la, lb, ep, st);
-    ks = last_ksplit();
-  } else if (VLP_LINW_BIG && M >= 65536) {
+    r = launch_gemm_pp<256, 256, 2, 4>(Nout, Kin, M, KSplit{linw_splits_pp(M, Nout, Kin), sp.max_ks, &ks}, la, lb,
+                                       ep, st);
+  } else {
+    const KSplit req{linw_splits(M, Nout, Kin), sp.max_ks, &ks};   // >= 256 token rows per split
     // deep token reductions with a short side (NesT levels 0 / 1: Nout or Kin = 96 / 192):
     // two K-tiles in flight (gemm_big_kernel) instead of the one-tile ring
-    r = VLP_LINW_BIG == 2 && Kin >= 256 ? launch_gemm_big<128, 256, 2, 4>(Nout, Kin, M, ks, la, lb, ep, st)
-                                        : launch_gemm_big<128, 128, 2, 2>(Nout, Kin, M, ks, la, lb, ep, st);
-    ks = last_ksplit();
-  } else {
-    r = launch_gemm_bk<128, 128, 2, 2>(Nout, Kin, M, ks, la, lb, ep, st);
+    if (VLP_LINW_BIG && M >= 65536)
+      r = VLP_LINW_BIG == 2 && Kin >= 256 ? launch_gemm_big<128, 256, 2, 4>(Nout, Kin, M, req, la, lb, ep, st)
+                                          : launch_gemm_big<128, 128, 2, 2>(Nout, Kin, M, req, la, lb, ep, st);
+    else
+      r = launch_gemm_bk<128, 128, 2, 2>(Nout, Kin, M, req, la, lb, ep, st);
   }
   if (r) return r;
   const size_t n4 = (size_t)Nout * Kin / 4;

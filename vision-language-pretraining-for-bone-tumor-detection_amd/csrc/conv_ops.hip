@@ -2176,6 +2176,17 @@ static int conv_wgrad_t(const void* dy, const void* x, float* dw, ConvGeom g, co
   ConvWgradB<T, false> lb{g, (const T*)x, nullptr, nullptr, g.K, make_pixstep(g, Elem<T>::BK)};
   return gemm_wgrad<T>(g.Co, g.K, g.M, la, lb, ep, st);
 }
+// The *_wgrad_ws entry points on an engine without per-split slabs (fp32 parity
+// mode): slab 0 [Co][ld] zeroed, then split-K with fp32 atomics into it; one slab.
+template <typename T, class LB>
+static int wgrad_atomic_slab0(int Co, int cols, int ld, int M, const void* dy, const LB& lb, float* ws, int* nsplit,
+                              hipStream_t st) {
+  if (hipMemsetAsync(ws, 0, (size_t)Co * ld * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
+  *nsplit = 1;
+  MNMat<T> la{(const T*)dy, Co, Co, M};
+  EpiAtomic ep{nullptr, nullptr, ws, ld, 1.0f};
+  return gemm_wgrad<T>(Co, cols, M, la, lb, ep, st);
+}
 
 // Weight gradient straight into the parameter's [Co][C][KH][KW] layout: the
 // GEMM's K-splits write fp32 slabs ws[s][Co][KH*KW*C] (EpiSplitStore) and one
@@ -2258,39 +2269,24 @@ static int conv_wgrad_ws_t(const void* dy, const void* x, float* ws, long long w
   g.M = g.N * g.Ho * g.Wo;
   g.K = g.KH * g.KW * g.C;
   const size_t slab = (size_t)g.Co * g.K;
-  const long long fit = ws_floats > 0 ? ws_floats / (long long)slab : 0;
-  const int max_ks = (int)(fit < 4096 ? fit : 4096);
-  if (max_ks < 1) return (int)hipErrorInvalidValue;
-  int ks = 1;
-  bool split_store = false;
+  const SlabPlan sp = plan_slabs(ws_floats, (long long)slab, g.M);
+  if (sp.max_ks < 1) return (int)hipErrorInvalidValue;
+  ConvWgradB<T, false> lb{g, (const T*)x, nullptr, nullptr, g.K, make_pixstep(g, Elem<T>::BK)};
   if constexpr (std::is_same<T, bf16>::value) {
     // layer 1: the row-streaming kernel, one slab per workgroup
-    if (wgrad_rows_ok(g)) return launch_wgrad_rows(g, dy, x, ws, max_ks, ks_out, st);
+    if (wgrad_rows_ok(g)) return launch_wgrad_rows(g, dy, x, ws, sp.max_ks, ks_out, st);
     // tile engines whose epilogue honours per-split output slabs
     if (g.K % 4 == 0) {
-      int mink = 2048;
-      const int need = (g.M + max_ks - 1) / max_ks;
-      if (mink < need) mink = need;
       static_assert(use_bk<bf16, MNMat<bf16>, ConvWgradB<bf16, false>>(),
                     "split slabs need the bk / big engines");
       MNMat<bf16> la{(const bf16*)dy, g.Co, g.Co, g.M};
-      ConvWgradB<bf16, false> lb{g, (const bf16*)x, nullptr, nullptr, g.K, make_pixstep(g, Elem<bf16>::BK)};
       EpiSplitStore ep{nullptr, nullptr, ws, g.K, slab};
-      const int r = g.Co <= 64 ? gemm_short<bf16>(g.Co, g.K, g.M, -mink, la, lb, ep, st)
-                               : gemm_conv_wide<bf16>(g.Co, g.K, g.M, -mink, la, lb, ep, st);
-      if (r) return r;
-      ks = last_ksplit();
-      if (ks > max_ks) return (int)hipErrorInvalidValue;   // would have overrun the workspace
-      split_store = true;
+      const KSplit ks{-sp.min_k, sp.max_ks, ks_out};
+      return g.Co <= 64 ? gemm_short<bf16>(g.Co, g.K, g.M, ks, la, lb, ep, st)
+                        : gemm_conv_wide<bf16>(g.Co, g.K, g.M, ks, la, lb, ep, st);
     }
   }
-  if (!split_store) {   // other engines: atomics into slab 0
-    if (hipMemsetAsync(ws, 0, slab * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
-    const int r = conv_wgrad_t<T>(dy, x, ws, g, nullptr, nullptr, st);
-    if (r) return r;
-  }
-  *ks_out = ks;
-  return 0;
+  return wgrad_atomic_slab0<T>(g.Co, g.K, g.K, g.M, dy, lb, ws, ks_out, st);   // other engines
 }
 
 static StemGeom make_stem(int N, int H, int W) {
@@ -2392,28 +2388,50 @@ __global__ void pack_stem1_kernel(const float* __restrict__ w, T* __restrict__ w
     v = w[((co * 3 + 0) * 7 + kh) * 7 + kw] + w[((co * 3 + 1) * 7 + kh) * 7 + kw] + w[((co * 3 + 2) * 7 + kh) * 7 + kw];
   wp[i] = from_f<T>(v);
 }
-// slabs [ks][64][64] of d/dW1 -> the parameter's [64][3][7][7] gradient: the three
-// channels carry identical images, so each receives the same gradient
-__global__ void __launch_bounds__(256) stem1_wgrad_fold_kernel(int ks, const float* __restrict__ ws,
-                                                               float* __restrict__ g) {
-  __shared__ float part[4][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;   // e < 64 * 64
-  const float* p = ws + e;
-  float a0 = 0.f, a1 = 0.f;
-  int s = grp;
-  for (; s + 4 < ks; s += 8) { a0 += p[(size_t)s * 64 * 64]; a1 += p[(size_t)(s + 4) * 64 * 64]; }
-  if (s < ks) a0 += p[(size_t)s * 64 * 64];
-  part[grp][threadIdx.x & 63] = a0 + a1;
-  __syncthreads();
-  if (grp == 0) {
-    const int co = e >> 6, kh = (e >> 3) & 7, kw = e & 7;
+// Slab layouts of the two stems' weight gradients: columns per output-channel row,
+// and where column k of row co lands in the parameter's [64][3][7][7] gradient.
+struct StemSlab {    // [64][kh:8][kw:8][c:4]
+  static constexpr int kCols = 256;
+  static __device__ void store(float* g, int co, int k, float v) {
+    const int kh = k >> 5, kw = (k >> 2) & 7, c = k & 3;
+    if (kh < 7 && kw < 7 && c < 3) g[((co * 3 + c) * 7 + kh) * 7 + kw] = v;
+  }
+};
+struct Stem1Slab {   // [64][kh:8][kw:8]: the three channels carry identical images, so each receives the same gradient
+  static constexpr int kCols = 64;
+  static __device__ void store(float* g, int co, int k, float v) {
+    const int kh = k >> 3, kw = k & 7;
     if (kh < 7 && kw < 7) {
-      const int l = threadIdx.x & 63;
-      const float v = (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]);
 #pragma unroll
       for (int c = 0; c < 3; ++c) g[((co * 3 + c) * 7 + kh) * 7 + kw] = v;
     }
   }
+};
+// per-split fp32 slabs [ks][64][L::kCols] (no atomics) folded straight into the
+// parameter's gradient: 64 slab elements x 4 slab groups per block: every wave
+// reads 256 contiguous bytes of one slab per step; the 4 group partials meet in
+// LDS (deterministic)
+template <class L>
+__global__ void __launch_bounds__(256) stem_wgrad_fold_kernel(int ks, const float* __restrict__ ws,
+                                                              float* __restrict__ g) {
+  constexpr size_t slab = 64 * L::kCols;
+  __shared__ float part[4][64];
+  const int l = threadIdx.x & 63, e = blockIdx.x * 64 + l, grp = threadIdx.x >> 6;   // e < slab
+  const float* p = ws + e;
+  float a0 = 0.f, a1 = 0.f;
+  int s = grp;
+  for (; s + 4 < ks; s += 8) { a0 += p[(size_t)s * slab]; a1 += p[(size_t)(s + 4) * slab]; }
+  if (s < ks) a0 += p[(size_t)s * slab];
+  part[grp][l] = a0 + a1;
+  __syncthreads();
+  if (grp == 0) L::store(g, e / L::kCols, e % L::kCols, (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]));
+}
+template <class L>
+static int stem_wgrad_fold(int nsplit, const float* split_ws, float* grad, void* stream) {
+  if (nsplit < 1) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(stem_wgrad_fold_kernel<L>, dim3(L::kCols), dim3(256), 0, (hipStream_t)stream, nsplit, split_ws,
+                     grad);
+  return (int)hipGetLastError();
 }
 
 }  // namespace vlp
@@ -2680,67 +2698,31 @@ VLP_EXPORT int vlp_stem_fwd(int dtype, const void* xp, const void* wp, void* y, 
   return launch_gemm<float, 256, 64, 4>(g.M, 64, 256, 1, la, lb, ep, st);
 }
 
-// dW_ws[64][256] (kh:8, kw:8, c:4 layout), fp32, accumulated atomically.
-VLP_EXPORT int vlp_stem_wgrad(int dtype, const void* dy, const void* xp, float* dw_ws, int N, int H, int W,
-                              void* stream);
-// stem weight gradient through per-split fp32 slabs [ks][64][256] (no atomics),
-// folded straight into the parameter's [64][3][7][7] gradient:
-// 64 slab elements x 4 slab groups per block: every wave reads 256 contiguous
-// bytes of one slab per step; the 4 group partials meet in LDS (deterministic)
-__global__ void __launch_bounds__(256) stem_wgrad_fold_kernel(int ks, const float* __restrict__ ws,
-                                                              float* __restrict__ g) {
-  __shared__ float part[4][64];
-  const int e = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;   // e < 64 * 256
-  const float* p = ws + e;
-  float a0 = 0.f, a1 = 0.f;
-  int s = grp;
-  for (; s + 4 < ks; s += 8) { a0 += p[(size_t)s * 64 * 256]; a1 += p[(size_t)(s + 4) * 64 * 256]; }
-  if (s < ks) a0 += p[(size_t)s * 64 * 256];
-  part[grp][threadIdx.x & 63] = a0 + a1;
-  __syncthreads();
-  if (grp == 0) {
-    const int co = e >> 8, k = e & 255, kh = k >> 5, kw = (k >> 2) & 7, c = k & 3;
-    if (kh < 7 && kw < 7 && c < 3) {
-      const int l = threadIdx.x & 63;
-      g[((co * 3 + c) * 7 + kh) * 7 + kw] = (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]);
-    }
-  }
-}
-
+// stem weight gradient through per-split fp32 slabs [ks][64][256] (no atomics) -> vlp_stem_wgrad_fold
+constexpr int kStemMaxSplits = 512;   // the stem folds then read <= 32 MB of slabs
 VLP_EXPORT int vlp_stem_wgrad_ws(int dtype, const void* dy, const void* xp, float* split_ws, long long ws_floats,
                                  int* nsplit, int N, int H, int W, void* stream) {
   StemGeom g = make_stem(N, H, W);
   hipStream_t st = (hipStream_t)stream;
   if (!nsplit || (long long)N * g.Hp * g.Wp * 4 >= (1ll << 31)) return (int)hipErrorInvalidValue;
-  const long long slab = 64 * 256;
-  const long long fit = ws_floats / slab;
-  const int max_ks = (int)(fit < 4096 ? fit : 4096);
-  if (max_ks < 1) return (int)hipErrorInvalidValue;
-  if (dtype != VLP_BF16) {   // fp32 parity mode: atomics into slab 0
-    if (hipMemsetAsync(split_ws, 0, slab * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
-    *nsplit = 1;
-    return vlp_stem_wgrad(dtype, dy, xp, split_ws, N, H, W, stream);
+  constexpr long long slab = 64 * StemSlab::kCols;
+  const SlabPlan sp = plan_slabs(ws_floats, slab, g.M, kStemMaxSplits);
+  if (sp.max_ks < 1) return (int)hipErrorInvalidValue;
+  if (dtype != VLP_BF16) {
+    StemWgradB<float> lb{g, (const float*)xp, make_stem_pixstep(g, Elem<float>::BK)};
+    return wgrad_atomic_slab0<float>(64, 224, StemSlab::kCols, g.M, dy, lb, split_ws, nsplit, st);
   }
-  // <= 512 splits: the fold then reads <= 32 MB of slabs
-  int mink = 2048;
-  const int need = (g.M + (max_ks < 512 ? max_ks : 512) - 1) / (max_ks < 512 ? max_ks : 512);
-  if (mink < need) mink = need;
   StemWgradB<bf16> lb{g, (const bf16*)xp, make_stem_pixstep(g, Elem<bf16>::BK)};
   MNMat<bf16> la{(const bf16*)dy, 64, 64, g.M};
-  EpiSplitStore ep{nullptr, nullptr, split_ws, 256, (size_t)slab};
-  const int r = launch_gemm_bk<64, 128, 1, 4>(64, 224, g.M, -mink, la, lb, ep, st);
-  if (r) return r;
-  *nsplit = last_ksplit();
-  return *nsplit > max_ks ? (int)hipErrorInvalidValue : 0;
+  EpiSplitStore ep{nullptr, nullptr, split_ws, StemSlab::kCols, (size_t)slab};
+  return launch_gemm_bk<64, 128, 1, 4>(64, 224, g.M, KSplit{-sp.min_k, sp.max_ks, nsplit}, la, lb, ep, st);
 }
 
 VLP_EXPORT int vlp_stem_wgrad_fold(int nsplit, const float* split_ws, float* grad, void* stream) {
-  if (nsplit < 1) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(stem_wgrad_fold_kernel, dim3(64 * 256 / 64), dim3(256), 0, (hipStream_t)stream, nsplit, split_ws,
-                     grad);
-  return (int)hipGetLastError();
+  return stem_wgrad_fold<StemSlab>(nsplit, split_ws, grad, stream);
 }
 
+// dW_ws[64][256] (kh:8, kw:8, c:4 layout), fp32, accumulated atomically.
 VLP_EXPORT int vlp_stem_wgrad(int dtype, const void* dy, const void* xp, float* dw_ws, int N, int H,
                               int W, void* stream) {
   StemGeom g = make_stem(N, H, W);
@@ -2813,33 +2795,19 @@ VLP_EXPORT int vlp_stem1_wgrad_ws(int dtype, const void* dy, const void* xs, flo
   Stem1Geom g = make_stem1(N, H, W);
   hipStream_t st = (hipStream_t)stream;
   if (!nsplit || g.Wo % 4) return (int)hipErrorInvalidValue;
-  const long long slab = 64 * 64;
-  const long long fit = ws_floats / slab;
-  const int max_ks = (int)(fit < 4096 ? fit : 4096);
-  if (max_ks < 1) return (int)hipErrorInvalidValue;
-  EpiSplitStore ep{nullptr, nullptr, split_ws, 64, (size_t)slab};
-  if (dtype != VLP_BF16) {   // fp32 parity mode: split-K with fp32 atomics into slab 0
-    if (hipMemsetAsync(split_ws, 0, slab * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
-    *nsplit = 1;
-    MNMat<float> la{(const float*)dy, 64, 64, g.M};
+  constexpr long long slab = 64 * Stem1Slab::kCols;
+  const SlabPlan sp = plan_slabs(ws_floats, slab, g.M, kStemMaxSplits);
+  if (sp.max_ks < 1) return (int)hipErrorInvalidValue;
+  if (dtype != VLP_BF16) {
     Stem1WgradB<float> lb{g, (const float*)xs, make_stem1_pixstep(g, Elem<float>::BK)};
-    EpiAtomic epa{nullptr, nullptr, split_ws, 64, 1.0f};
-    return gemm_wgrad<float>(64, 56, g.M, la, lb, epa, st);
+    return wgrad_atomic_slab0<float>(64, 56, Stem1Slab::kCols, g.M, dy, lb, split_ws, nsplit, st);
   }
-  int mink = 2048;
-  const int need = (g.M + (max_ks < 512 ? max_ks : 512) - 1) / (max_ks < 512 ? max_ks : 512);
-  if (mink < need) mink = need;
   Stem1WgradB<bf16> lb{g, (const bf16*)xs, make_stem1_pixstep(g, Elem<bf16>::BK)};
   MNMat<bf16> la{(const bf16*)dy, 64, 64, g.M};
-  const int r = launch_gemm_bk<64, 64, 1, 4>(64, 56, g.M, -mink, la, lb, ep, st);
-  if (r) return r;
-  *nsplit = last_ksplit();
-  return *nsplit > max_ks ? (int)hipErrorInvalidValue : 0;
+  EpiSplitStore ep{nullptr, nullptr, split_ws, Stem1Slab::kCols, (size_t)slab};
+  return launch_gemm_bk<64, 64, 1, 4>(64, 56, g.M, KSplit{-sp.min_k, sp.max_ks, nsplit}, la, lb, ep, st);
 }
 
 VLP_EXPORT int vlp_stem1_wgrad_fold(int nsplit, const float* split_ws, float* grad, void* stream) {
-  if (nsplit < 1) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(stem1_wgrad_fold_kernel, dim3(64 * 64 / 64), dim3(256), 0, (hipStream_t)stream, nsplit,
-                     split_ws, grad);
-  return (int)hipGetLastError();
+  return stem_wgrad_fold<Stem1Slab>(nsplit, split_ws, grad, stream);
 }

@@ -1440,13 +1440,6 @@ gemm_pp_kernel(GemmShape sh, LA la, LB lb, EP ep) {
   }
 }
 
-// split count of the last launch_gemm_bk / launch_gemm_big / launch_gemm_pp
-// call on this host thread (callers of split-store epilogues size their fold
-// pass with it)
-inline int& last_ksplit() {
-  static thread_local int v = 1;
-  return v;
-}
 // Split-K count for a reduction of K over `tiles` output tiles, given the
 // number of workgroups the chip holds at once (`slots`).  Workgroups of one
 // launch all cost about the same, so the launch takes ceil(WG / slots)
@@ -1472,6 +1465,52 @@ inline int balanced_ksplit(int tiles, int K, int slots, int min_k) {
     if (eff > best_eff + 0.01) { best_eff = eff; best = ks; }
   }
   return best;
+}
+// What a launcher is asked about its reduction split.  `request` > 0 is an explicit
+// count; <= 0 asks for the slot-balanced count with at least -request elements of
+// K per split (0: 2048).  `bound` caps the count whatever the request (the slabs
+// the epilogue may write), and `count`, when set, receives the count launched
+// with.  An int converts to a request without a bound.
+struct KSplit {
+  int request;
+  int bound = 1 << 30;
+  int* count = nullptr;
+  KSplit(int r) : request(r) {}
+  KSplit(int r, int b, int* c) : request(r), bound(b), count(c) {}
+};
+struct KSplitPlan { int count, chunk; };
+// The one place a split is decided, before anything is launched: the count
+// (balanced_ksplit over `slots` resident workgroups for an auto request), capped
+// at the bound, then the chunk = ceil(K / count) rounded up to BK, then the count
+// the chunks really make.  The rounding only lowers the count (the chunk only
+// grows, and ceil(K / ceil(K / n)) <= n), so the result is never above the bound.
+// On the auto path the bound cannot bind when the caller requests
+// min_k >= ceil(K / bound): balanced_ksplit only returns 1 or a count with
+// K / count >= min_k (its shallow branch returns K / min_k), so
+// count <= K / min_k <= K / ceil(K / bound) <= bound.
+inline KSplitPlan resolve_ksplit(const KSplit& req, int K, int tiles, int slots, int BK) {
+  int n = req.request > 0 ? req.request : balanced_ksplit(tiles, K, slots, req.request < 0 ? -req.request : 2048);
+  if (n > req.bound) n = req.bound;
+  if (n < 1) n = 1;
+  int kc = (K + n - 1) / n;
+  kc = ((kc + BK - 1) / BK) * BK;
+  if (kc < BK) kc = BK;
+  n = (K + kc - 1) / kc;
+  if (n < 1) n = 1;
+  if (req.count) *req.count = n;
+  return {n, kc};
+}
+// Slab plan of a split-K reduction of length K whose splits each store one fp32
+// slab of `slab` floats into a workspace of `ws_floats`: how many slabs the
+// split may write (those that fit, at most `ceiling` and 4096; 0: none fits) and
+// the min_k request (>= 2048) that keeps the auto split within them.
+struct SlabPlan { int max_ks, min_k; };
+inline SlabPlan plan_slabs(long long ws_floats, long long slab, int K, int ceiling = 4096) {
+  const long long fit = ws_floats > 0 ? ws_floats / slab : 0;
+  const int cap = ceiling < 4096 ? ceiling : 4096;
+  const int max_ks = (int)(fit < cap ? fit : cap);
+  const int need = max_ks > 0 ? (K + max_ks - 1) / max_ks : 0;
+  return {max_ks, need > 2048 ? need : 2048};
 }
 // current device index (per-device caches of per-function launch state)
 inline int cur_dev() {
@@ -1515,7 +1554,7 @@ inline int prepare_kernel(KernelDevState& s, const void* fn, int lds, int thread
 }
 
 template <int BM, int BN, int WGM, int WGN, class LA, class LB, class EP>
-inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int launch_gemm_bk(int M, int N, int K, KSplit ks, const LA& la, const LB& lb, const EP& ep,
                           hipStream_t stream) {
   constexpr int BK = 64;
   constexpr int S = 2;
@@ -1528,22 +1567,17 @@ inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const L
   constexpr int lds = S * (BM + BN) * 128;
   static_assert(lds <= 160 * 1024, "LDS budget");
   static KernelDevState kst;
-  if (ksplit <= 0) {   // auto: fill whole rounds of resident workgroups
+  int slots = 0;
+  if (ks.request <= 0) {   // auto: fill whole rounds of resident workgroups
     int occ = 1;
     const int e = prepare_kernel(kst, (const void*)&gemm_bk_kernel<BM, BN, WGM, WGN, LA, LB, EP>, lds, WGM * WGN * 64, &occ);
     if (e) return e;
-    ksplit = balanced_ksplit(sh.tiles_m * sh.tiles_n, K, occ * device_cus(), -ksplit > 0 ? -ksplit : 2048);
+    slots = occ * device_cus();
   }
-  if (ksplit < 1) ksplit = 1;
-  int kc = (K + ksplit - 1) / ksplit;
-  kc = ((kc + BK - 1) / BK) * BK;
-  if (kc < BK) kc = BK;
-  ksplit = (K + kc - 1) / kc;
-  if (ksplit < 1) ksplit = 1;
-  sh.kchunk = kc;
-  sh.nsplit = ksplit;
-  last_ksplit() = ksplit;
-  dim3 grid(sh.tiles_m * sh.tiles_n * ksplit, 1, 1);
+  const KSplitPlan plan = resolve_ksplit(ks, K, sh.tiles_m * sh.tiles_n, slots, BK);
+  sh.kchunk = plan.chunk;
+  sh.nsplit = plan.count;
+  dim3 grid(sh.tiles_m * sh.tiles_n * plan.count, 1, 1);
   {
     const int e = prepare_kernel(kst, (const void*)&gemm_bk_kernel<BM, BN, WGM, WGN, LA, LB, EP>, lds, 0, nullptr);
     if (e) return e;
@@ -1554,7 +1588,7 @@ inline int launch_gemm_bk(int M, int N, int K, int ksplit, const LA& la, const L
 }
 
 template <int BM, int BN, int WGM, int WGN, class LA, class LB, class EP, int WPE = VLP_WAVES_PER_EU>
-inline int launch_gemm_big(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int launch_gemm_big(int M, int N, int K, KSplit ks, const LA& la, const LB& lb, const EP& ep,
                           hipStream_t stream) {
   constexpr int BK = 64;
   constexpr int S = 2;
@@ -1567,22 +1601,17 @@ inline int launch_gemm_big(int M, int N, int K, int ksplit, const LA& la, const 
   constexpr int lds = big_lds_bytes<BM, BN, EP>();
   static_assert(lds <= 160 * 1024, "LDS budget");
   static KernelDevState kst;
-  if (ksplit <= 0) {   // auto: fill whole rounds of resident workgroups
+  int slots = 0;
+  if (ks.request <= 0) {   // auto: fill whole rounds of resident workgroups
     int occ = 1;
     const int e = prepare_kernel(kst, (const void*)&gemm_big_kernel<BM, BN, WGM, WGN, LA, LB, EP, WPE>, lds, WGM * WGN * 64, &occ);
     if (e) return e;
-    ksplit = balanced_ksplit(sh.tiles_m * sh.tiles_n, K, occ * device_cus(), -ksplit > 0 ? -ksplit : 2048);
+    slots = occ * device_cus();
   }
-  if (ksplit < 1) ksplit = 1;
-  int kc = (K + ksplit - 1) / ksplit;
-  kc = ((kc + BK - 1) / BK) * BK;
-  if (kc < BK) kc = BK;
-  ksplit = (K + kc - 1) / kc;
-  if (ksplit < 1) ksplit = 1;
-  sh.kchunk = kc;
-  sh.nsplit = ksplit;
-  last_ksplit() = ksplit;
-  dim3 grid(sh.tiles_m * sh.tiles_n * ksplit, 1, 1);
+  const KSplitPlan plan = resolve_ksplit(ks, K, sh.tiles_m * sh.tiles_n, slots, BK);
+  sh.kchunk = plan.chunk;
+  sh.nsplit = plan.count;
+  dim3 grid(sh.tiles_m * sh.tiles_n * plan.count, 1, 1);
   {
     const int e = prepare_kernel(kst, (const void*)&gemm_big_kernel<BM, BN, WGM, WGN, LA, LB, EP, WPE>, lds, 0, nullptr);
     if (e) return e;
@@ -1593,7 +1622,7 @@ inline int launch_gemm_big(int M, int N, int K, int ksplit, const LA& la, const 
 }
 
 template <int BM, int BN, int WGM, int WGN, class LA, class LB, class EP>
-inline int launch_gemm_pp(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int launch_gemm_pp(int M, int N, int K, KSplit ks, const LA& la, const LB& lb, const EP& ep,
                           hipStream_t stream) {
   constexpr int BK = 64;
   if (M <= 0 || N <= 0) return 0;
@@ -1604,22 +1633,17 @@ inline int launch_gemm_pp(int M, int N, int K, int ksplit, const LA& la, const L
   constexpr int lds = big_lds_bytes<BM, BN, EP>() + (XformTrait<LA>::value ? 4096 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
   static KernelDevState kst;
-  if (ksplit <= 0) {   // auto: fill whole rounds of resident workgroups
+  int slots = 0;
+  if (ks.request <= 0) {   // auto: fill whole rounds of resident workgroups
     int occ = 1;
     const int e = prepare_kernel(kst, (const void*)&gemm_pp_kernel<BM, BN, WGM, WGN, LA, LB, EP>, lds, WGM * WGN * 64, &occ);
     if (e) return e;
-    ksplit = balanced_ksplit(sh.tiles_m * sh.tiles_n, K, occ * device_cus(), -ksplit > 0 ? -ksplit : 2048);
+    slots = occ * device_cus();
   }
-  if (ksplit < 1) ksplit = 1;
-  int kc = (K + ksplit - 1) / ksplit;
-  kc = ((kc + BK - 1) / BK) * BK;
-  if (kc < BK) kc = BK;
-  ksplit = (K + kc - 1) / kc;
-  if (ksplit < 1) ksplit = 1;
-  sh.kchunk = kc;
-  sh.nsplit = ksplit;
-  last_ksplit() = ksplit;
-  dim3 grid(sh.tiles_m * sh.tiles_n * ksplit, 1, 1);
+  const KSplitPlan plan = resolve_ksplit(ks, K, sh.tiles_m * sh.tiles_n, slots, BK);
+  sh.kchunk = plan.chunk;
+  sh.nsplit = plan.count;
+  dim3 grid(sh.tiles_m * sh.tiles_n * plan.count, 1, 1);
   {
     const int e = prepare_kernel(kst, (const void*)&gemm_pp_kernel<BM, BN, WGM, WGN, LA, LB, EP>, lds, 0, nullptr);
     if (e) return e;
@@ -1635,7 +1659,7 @@ constexpr int gemm_lds_bytes() { return 2 * (BM + BN) * 128; }
 // Host-side launcher of the register-staged gemm_kernel.  ksplit > 1 splits the
 // reduction over grid.y (the epilogue must then accumulate atomically).
 template <typename T, int BM, int BN, int WGM, class LA, class LB, class EP>
-inline int launch_gemm(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int launch_gemm(int M, int N, int K, KSplit ks, const LA& la, const LB& lb, const EP& ep,
                        hipStream_t stream) {
   constexpr int BK = Elem<T>::BK;
   if (M <= 0 || N <= 0) return 0;
@@ -1644,20 +1668,16 @@ inline int launch_gemm(int M, int N, int K, int ksplit, const LA& la, const LB& 
   sh.M = M; sh.N = N; sh.K = K;
   sh.tiles_m = (M + BM - 1) / BM;
   sh.tiles_n = (N + BN - 1) / BN;
-  if (ksplit <= 0) {   // auto: ~1024 workgroups, >= 4096-deep splits
+  if (ks.request <= 0) {   // this engine's own auto: ~1024 workgroups, >= 4096-deep splits
     const int tiles = sh.tiles_m * sh.tiles_n;
-    ksplit = (1024 + tiles - 1) / tiles;
+    ks.request = (1024 + tiles - 1) / tiles;
     const int max_split = (K + 4095) / 4096;
-    if (ksplit > max_split) ksplit = max_split;
+    if (ks.request > max_split) ks.request = max_split;
+    if (ks.request < 1) ks.request = 1;
   }
-  if (ksplit < 1) ksplit = 1;
-  int kc = (K + ksplit - 1) / ksplit;
-  kc = ((kc + BK - 1) / BK) * BK;
-  if (kc < BK) kc = BK;
-  ksplit = (K + kc - 1) / kc;
-  if (ksplit < 1) ksplit = 1;
-  sh.kchunk = kc;
-  dim3 grid(sh.tiles_m * sh.tiles_n, ksplit, 1);
+  const KSplitPlan plan = resolve_ksplit(ks, K, sh.tiles_m * sh.tiles_n, 0, BK);
+  sh.kchunk = plan.chunk;
+  dim3 grid(sh.tiles_m * sh.tiles_n, plan.count, 1);
   constexpr int lds = gemm_lds_bytes<T, BM, BN>();
   static KernelDevState kst;
   {
@@ -1681,7 +1701,7 @@ constexpr bool use_bk() {
 // large-tile shape choice: 256x256 (8 waves, one workgroup per CU) when both
 // dimensions allow it, else 128x256, and 128x128 (4 waves) for N = 128
 template <class LA, class LB, class EP>
-inline int gemm_big_auto(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
+inline int gemm_big_auto(int M, int N, int K, KSplit ksplit, const LA& la, const LB& lb, const EP& ep, hipStream_t st) {
   // (256x256 keeps 128x64 fragments per wave live: only the all-K-contig case
   // fits the 256-VGPR budget without spilling)
   // ping-pong schedule (gemm_pp_kernel) for K-contig x K-contig and MN x MN
@@ -1712,7 +1732,7 @@ inline int gemm_big_auto(int M, int N, int K, int ksplit, const LA& la, const LB
 }
 // N >= 128 columns
 template <typename T, class LA, class LB, class EP>
-inline int gemm_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int gemm_wide(int M, int N, int K, KSplit ksplit, const LA& la, const LB& lb, const EP& ep,
                      hipStream_t st) {
   if constexpr (use_bk<T, LA, LB>()) return launch_gemm_bk<128, 128, 2, 2>(M, N, K, ksplit, la, lb, ep, st);
   else return launch_gemm<T, 128, 128, 2>(M, N, K, ksplit, la, lb, ep, st);
@@ -1720,7 +1740,7 @@ inline int gemm_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb
 // convolution GEMMs with N >= 128 (and M >= 128): the large-tile kernels
 // where both loaders speak the buffer protocol
 template <typename T, class LA, class LB, class EP>
-inline int gemm_conv_wide(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int gemm_conv_wide(int M, int N, int K, KSplit ksplit, const LA& la, const LB& lb, const EP& ep,
                           hipStream_t st) {
   if constexpr (use_bk<T, LA, LB>()) return gemm_big_auto(M, N, K, ksplit, la, lb, ep, st);
   else return gemm_wide<T>(M, N, K, ksplit, la, lb, ep, st);
@@ -1734,7 +1754,7 @@ inline int gemm_narrow(int M, int N, int K, int ksplit, const LA& la, const LB& 
 }
 // M <= 64 rows (weight gradients of Co = 64 convs)
 template <typename T, class LA, class LB, class EP>
-inline int gemm_short(int M, int N, int K, int ksplit, const LA& la, const LB& lb, const EP& ep,
+inline int gemm_short(int M, int N, int K, KSplit ksplit, const LA& la, const LB& lb, const EP& ep,
                       hipStream_t st) {
   if constexpr (use_bk<T, LA, LB>()) {
     // 64 x 192 tiles (3 taps of 64 channels) on the two-K-tiles-in-flight engine:

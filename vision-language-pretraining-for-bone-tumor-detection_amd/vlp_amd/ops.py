@@ -6,6 +6,8 @@ All functions enqueue on torch's current stream and never synchronise.
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import ktimer
@@ -197,38 +199,39 @@ def wgrad_ws(device):
     return _stream_ws("wgrad", device, WGRAD_WS_FLOATS)
 
 
+def _wgrad_into(entry, label, flops, dy, x, geom, fold_geom, grad):
+    """The shared body of the *_wgrad_into wrappers:
+    vlp_<entry>_wgrad_ws(dtype, dy, x, ws, ws floats, &nsplit, *geom, stream) timed under `label`,
+    its K-splits stored as fp32 slabs of the stream's cached workspace, then
+    vlp_<entry>_wgrad_fold(*fold_geom, nsplit, ws, grad, stream) with the split count the
+    first call returned."""
+    ws = wgrad_ws(dy.device)
+    ns = ctypes.c_int(0)
+    tk = ktimer.begin(label, flops)
+    getattr(lib(), f"vlp_{entry}_wgrad_ws")(dcode(dy), ptr(dy), ptr(x), ptr(ws), ws.numel(), ctypes.addressof(ns),
+                                            *geom, _s())
+    ktimer.end(tk)
+    getattr(lib(), f"vlp_{entry}_wgrad_fold")(*fold_geom, ns.value, ptr(ws), ptr(grad), _s())
+    return grad
+
+
 def conv_wgrad_into(dy, x, KH, KW, S, P, grad):
     """grad[Co][C][KH][KW] = sum over pixels dy x_patch, overwriting grad (the
     parameter's own gradient layout).  The GEMM's K-splits write fp32 slabs of
     a cached workspace; one fold pass sums and transposes them."""
-    import ctypes
     N, H, W, C = x.shape
     Co, Ho, Wo = dy.shape[-1], dy.shape[1], dy.shape[2]
-    ws = wgrad_ws(dy.device)
-    ns = ctypes.c_int(0)
-    tk = ktimer.begin(f"conv_wgrad[raw]{_tile_wgrad(Co)}", 2.0 * N * Ho * Wo * Co * C * KH * KW)
-    lib().vlp_conv_wgrad_ws(dcode(dy), ptr(dy), ptr(x), ptr(ws), ws.numel(), ctypes.addressof(ns), N, H, W, C,
-                            Co, KH, KW, S, P, _s())
-    ktimer.end(tk)
-    lib().vlp_conv_wgrad_fold(Co, C, KH, KW, ns.value, ptr(ws), ptr(grad), _s())
-    return grad
+    return _wgrad_into("conv", f"conv_wgrad[raw]{_tile_wgrad(Co)}", 2.0 * N * Ho * Wo * Co * C * KH * KW, dy, x,
+                       (N, H, W, C, Co, KH, KW, S, P), (Co, C, KH, KW), grad)
 
 
 def stem_wgrad_into(dy, xp, N, H, W, grad):
     """grad[64][3][7][7] = stem weight gradient (overwrites), via per-split
     fp32 slabs of the shared weight-gradient workspace and one fold pass."""
-    import ctypes
-    ws = wgrad_ws(dy.device)
-    ns = ctypes.c_int(0)
-    tk = ktimer.begin("stem_wgrad", 2.0 * dy.numel() * 147)
-    lib().vlp_stem_wgrad_ws(dcode(dy), ptr(dy), ptr(xp), ptr(ws), ws.numel(), ctypes.addressof(ns), N, H, W, _s())
-    ktimer.end(tk)
-    lib().vlp_stem_wgrad_fold(ns.value, ptr(ws), ptr(grad), _s())
-    return grad
+    return _wgrad_into("stem", "stem_wgrad", 2.0 * dy.numel() * 147, dy, xp, (N, H, W), (), grad)
 
 
 def stem_geom(H, W):
-    import ctypes
     a, b, c, d = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int())
     lib()._dll.vlp_stem_geom(H, W, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                              ctypes.byref(d))
@@ -238,7 +241,6 @@ def stem_geom(H, W):
 def stem1_geom(H, W):
     """(Ho, Wo, Hp, Wp1) of the single-channel stem, or None when it does not apply
     (Wo % 4 != 0: the caller takes the 3-channel path)."""
-    import ctypes
     a, b, c, d = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int())
     r = lib()._dll.vlp_stem1_geom(H, W, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d))
     return None if r else (a.value, b.value, c.value, d.value)
@@ -262,14 +264,7 @@ def stem1_fwd(xs, wp1, N, H, W, y, stat_sum, stat_sumsq, stat_rep=1):
 
 def stem1_wgrad_into(dy, xs, N, H, W, grad):
     """grad[64][3][7][7] = stem weight gradient of the single-channel path (overwrites)."""
-    import ctypes
-    ws = wgrad_ws(dy.device)
-    ns = ctypes.c_int(0)
-    tk = ktimer.begin("stem_wgrad", 2.0 * dy.numel() * 147)
-    lib().vlp_stem1_wgrad_ws(dcode(dy), ptr(dy), ptr(xs), ptr(ws), ws.numel(), ctypes.addressof(ns), N, H, W, _s())
-    ktimer.end(tk)
-    lib().vlp_stem1_wgrad_fold(ns.value, ptr(ws), ptr(grad), _s())
-    return grad
+    return _wgrad_into("stem1", "stem_wgrad", 2.0 * dy.numel() * 147, dy, xs, (N, H, W), (), grad)
 
 
 def stem1_fused_ok(H, W):
@@ -294,7 +289,6 @@ def stem1_bwd_fused_into(xs, wp1, dp, idx, mean, istd, gamma, sum_g, sum_gx, N, 
     (ReLU-masked): routing, BN backward and the weight gradient in one pass
     through the batch sums R = sum g P^T, G = sum P P^T, S = sum P (y0 and dy
     never formed); per-workgroup slabs folded in a fixed order."""
-    import ctypes
     n = ctypes.c_longlong(0)
     lib().vlp_stem1_bwd_fused_ws_floats(N, H, W, ctypes.byref(n))
     ws = _stream_ws("wgrad", dp.device, max(n.value, WGRAD_WS_FLOATS))
@@ -446,8 +440,7 @@ def linear_wgrad(dy, x, dw, M, Nout, Kin, lddy=None, ldx=None):
     workspace folded by one reduction pass; fp32: atomic split-K."""
     tk = ktimer.begin("linear_wgrad/wide", 2.0 * M * Nout * Kin)
     if dy.dtype == torch.bfloat16 and Kin % 4 == 0:
-        import ctypes
-        n = ctypes.c_longlong(0)
+        n =ctypes.c_longlong(0)
         lib().vlp_linear_wgrad_ws_floats(M, Nout, Kin, ctypes.byref(n))
         ws = _linw_ws(dy.device, max(n.value, 16 * Nout * Kin))
         lib().vlp_linear_wgrad_ws(dcode(dy), M, Nout, Kin, ptr(dy), lddy or Nout, ptr(x), ldx or Kin,
@@ -523,7 +516,6 @@ def clip_loss_fused(B, N, E, offset, img_all, txt_all, logit_scale, g_img_all, g
                     loss_parts, lse_out=None, role_w=None):
     """Global-batch symmetric InfoNCE + gradients (three launches, split over key
     chunks; the scratch is a per-(device, stream) cached workspace)."""
-    import ctypes
     n = ctypes.c_longlong(0)
     lib().vlp_clip_loss_ws_floats(B, N, E, ctypes.addressof(n))
     ws = _stream_ws("clip", img_all.device, n.value)
@@ -542,7 +534,6 @@ def clip_loss_fused_masked(B, N, E, offset, img_all, txt_all, logit_scale, cid_a
                            d_ls, loss_parts, lse_out=None, role_w=None):
     """clip_loss_fused without the duplicate-caption negatives: cid_all int32 [N], entries
     (i, j), i != j, with equal ids are left out of both softmaxes (same workspace)."""
-    import ctypes
     _check_cid(cid_all, N)
     n = ctypes.c_longlong(0)
     lib().vlp_clip_loss_ws_floats(B, N, E, ctypes.addressof(n))
@@ -595,7 +586,6 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step):
 
 def grad_sumsq_nparts(n):
     """Number of fp64 partials vlp_grad_sumsq writes for an n-element span."""
-    import ctypes
     k = ctypes.c_int(0)
     lib().vlp_grad_sumsq_nparts(int(n), ctypes.byref(k))
     return k.value
@@ -604,7 +594,6 @@ def grad_sumsq_nparts(n):
 def grad_sumsq(g, partials, offset=0):
     """fp64 partial sums of g^2 into partials[offset:]; returns how many were written
     (replaces the per-tensor norms of torch.nn.utils.clip_grad_norm_)."""
-    import ctypes
     if g.dtype != torch.float32 or partials.dtype != torch.float64 or not g.is_contiguous():
         raise TypeError("grad_sumsq: contiguous fp32 gradients and fp64 partials")
     if offset < 0 or offset + grad_sumsq_nparts(g.numel()) > partials.numel():
@@ -647,7 +636,6 @@ def grad_accum(acc, g, w=1.0, first=False):
 def grad_accum_sumsq(acc, g, w, partials, offset=0):
     """grad_sumsq of acc + w * g (which is not stored) into partials[offset:]; returns how many
     partials were written."""
-    import ctypes
     _f32_flat("grad_accum_sumsq", acc, g)
     if partials.dtype != torch.float64:
         raise TypeError("grad_accum_sumsq: fp64 partials")
@@ -690,7 +678,6 @@ def pack_conv(w, wp, wt):
 def pack_conv_batch(dtype_ref, entries):
     """entries: [(w fp32 [Co][C][KH][KW], wp, wt)] packed in one launch.
     Returns the ctypes descriptor table (reusable with pack_conv_batch_run)."""
-    import ctypes
     rows = []
     for w, wp, wt in entries:
         Co, C, KH, KW = w.shape
@@ -701,7 +688,6 @@ def pack_conv_batch(dtype_ref, entries):
 
 
 def pack_conv_batch_run(desc):
-    import ctypes
     code, n, table = desc
     lib().vlp_pack_conv_batch(code, n, ctypes.addressof(table), _s())
 

@@ -240,14 +240,6 @@ class ResNet34Tower(ArenaModule):
                     ws[cd.key + ".wt"] = buf[n1:].view(cd.C, 1, 1, cd.Co)
                 else:
                     ws[c.key + ".wt"] = torch.empty(c.C, c.KH, c.KW, c.Co, dtype=T, device=dev)
-        # wgrad workspaces (fp32, GEMM layout), one flat buffer zeroed per backward
-        off = 0
-        self._wg_off = {}
-        for c in self._convs.values():
-            n = 64 * 256 if c.key == "conv1" else c.numel
-            self._wg_off[c.key] = (off, n)
-            off += (n + 63) // 64 * 64
-        ws["wgrad"] = torch.zeros(off, dtype=torch.float32, device=dev)
         # per-BN coefficient and statistic slices
         nb = len(self._bns)
         Cmax = 512
@@ -606,7 +598,7 @@ class ResNet34Tower(ArenaModule):
             ops.bn_grad_rep(STAT_REP, C, sg1f, sgx1f, self.arena.gview(k1 + ".weight"),
                             self.arena.gview(k1 + ".bias"))
             sg1, sgx1 = sg1f[:C], sgx1f[:C]
-            self._wgrad(ws, c2, dy2, B["a1"])
+            self._wgrad(c2, dy2, B["a1"])
             dy1 = dy_pair[0] if dy_pair is not None else torch.empty_like(y1)
             if fuse_in:
                 ops.bn_bwd_coef(M, self.arena.view(k1 + ".weight"), is1, mu1, sg1, sgx1, coef[1])
@@ -619,7 +611,7 @@ class ResNet34Tower(ArenaModule):
                 cd = self._convs[pre + ".downsample.0"]
                 if not ds_fold:
                     addend = ops.conv_dgrad(dyd, ws[cd.key + ".wt"], Hi, Wi, Cin, 1, 1, cd.S, 0)
-                self._wgrad(ws, cd, dyd, x)
+                self._wgrad(cd, dyd, x)
             # the gradient reaching block bi-1 passes its output ReLU and feeds its bn2:
             # when that block has no downsample branch, mask + reduce in this epilogue
             if stem_sums:
@@ -675,7 +667,7 @@ class ResNet34Tower(ArenaModule):
                     raise RuntimeError(f"{pre}: fused BN-backward input without a fused data-gradient epilogue")
                 dx = ops.conv_dgrad(dy1, ws[c1.key + ".wt"], Hi, Wi, Cin, 3, 3, c1.S, 1, addend=addend)
                 dout_masked = False
-            self._wgrad(ws, c1, dy1, x)
+            self._wgrad(c1, dy1, x)
             if self._dbg is not None:
                 self._dbg[pre + "/dy2"] = (dy2.detach().clone(), False)
                 self._dbg[pre + "/g1"] = (g1.detach().clone(), False)
@@ -721,25 +713,18 @@ class ResNet34Tower(ArenaModule):
                                 self.arena.gview("conv1.weight"))
         self._stage_done(["layer1", "stem"], on_stage_done, dev)
 
-    def _wgrad(self, ws, c, dy, x, sc=None, sh=None):
-        if sc is None:
-            sw = getattr(self, "_sw", None)
-            if sw is not None:
-                # fork onto the weight-gradient stream; the allocator must not
-                # recycle dy / x before that stream has read them
-                sw.wait_stream(torch.cuda.current_stream(dy.device))
-                with torch.cuda.stream(sw):
-                    ops.conv_wgrad_into(dy, x, c.KH, c.KW, c.S, c.P, self.arena.gview(c.key + ".weight"))
-                dy.record_stream(sw)
-                x.record_stream(sw)
-                return
-            ops.conv_wgrad_into(dy, x, c.KH, c.KW, c.S, c.P, self.arena.gview(c.key + ".weight"))
+    def _wgrad(self, c, dy, x):
+        sw = getattr(self, "_sw", None)
+        if sw is not None:
+            # fork onto the weight-gradient stream; the allocator must not
+            # recycle dy / x before that stream has read them
+            sw.wait_stream(torch.cuda.current_stream(dy.device))
+            with torch.cuda.stream(sw):
+                ops.conv_wgrad_into(dy, x, c.KH, c.KW, c.S, c.P, self.arena.gview(c.key + ".weight"))
+            dy.record_stream(sw)
+            x.record_stream(sw)
             return
-        o, n = self._wg_off[c.key]
-        buf = ws["wgrad"][o:o + n]
-        buf.zero_()
-        ops.conv_wgrad(dy, x, c.KH, c.KW, c.S, c.P, buf, sc, sh)
-        ops.unpack_conv_grad(buf, self.arena.gview(c.key + ".weight"))
+        ops.conv_wgrad_into(dy, x, c.KH, c.KW, c.S, c.P, self.arena.gview(c.key + ".weight"))
 
     # ---------------- autograd entry ----------------
     def forward(self, x):
