@@ -1,6 +1,7 @@
-"""Helpers shared by tests/test_gpu_text_routes.py and tests/test_gpu_flash_routes.py: storage
-dtypes, the dropout hash of csrc/common.h on the host, NaN-guarded buffers and the per-element
-gate.  No tests and no fixtures live here."""
+"""Helpers shared by tests/test_gpu_text_routes.py, tests/test_gpu_flash_routes.py and
+tests/test_gpu_stem_routes.py: storage dtypes, the dropout hash of csrc/common.h on the host,
+NaN-guarded buffers, the per-element gate, and (stem suite) the staged-rounding and sum bounds.
+No tests and no fixtures live here."""
 import numpy as np
 import torch
 
@@ -88,3 +89,35 @@ def check_into(worst, name, fam, got, ref, bound):
     worst[fam] = max(worst.get(fam, 0.0), ratio)
     print(f"{name}: worst |err|/bound {ratio:.3f}, violations {nviol} of {ref.numel()}")
     assert nviol == 0, f"{name}: {nviol} of {ref.numel()} elements beyond the bound (worst ratio {ratio:.2f})"
+
+
+# ---------------------------------------------------------------- staged roundings and sums (stem suite)
+EPS32 = 2.0 ** -23
+
+
+def staged(acc64, noise):
+    """bf16(acc64) and, per element, what a flip of that rounding may move it by: one ulp where acc64
+    lies within `noise` of a rounding boundary (where fp32 and fp64 accumulation can round apart),
+    zero elsewhere (the convolution suite's `staged`)."""
+    v = acc64.to(BF16).double()
+    m, e = torch.frexp(v.abs())
+    ulp = torch.ldexp(torch.ones_like(v), e - 8) * (v != 0)
+    d = (acc64 - v).abs()
+    near = (ulp / 2 - d) <= noise
+    near |= (m == 0.5) & ((ulp / 4 - d).abs() <= noise)   # below a power of two the spacing halves
+    return v, torch.where(near, ulp, torch.zeros_like(ulp))
+
+
+def sum_bound(noise_f, gf, T, dims):
+    """2 * (sum noise * |f| + (T + 4) * eps32 * sum |g * f|) over `dims`: the per-element deviation carried
+    linearly into a sum whose fp32 partials are T terms deep (the convolution suite's `sum_bound`)."""
+    return 2.0 * (noise_f.sum(dims) + (T + 4) * EPS32 * gf.abs().sum(dims))
+
+
+def emu_sum(v32, T):
+    """[rows][C] fp32 -> [C] fp64: fp32 partial sums of T rows, then fp64 (a kernel's reduction, emulated)"""
+    v = v32.reshape(-1, v32.shape[-1])
+    pad = (-v.shape[0]) % T
+    if pad:
+        v = torch.cat([v, torch.zeros(pad, v.shape[1], dtype=v.dtype)])
+    return v.view(-1, T, v.shape[1]).sum(1).double().sum(0)
