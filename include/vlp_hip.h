@@ -533,6 +533,42 @@ int vlp_binmetric_pairs(int n, const float* scores, const unsigned char* labels,
 int vlp_binmetric_fold(int nparts, const unsigned long long* parts, const long long* counts, long long* out,
                        void* stream);
 
+/* ---------------- the baselines' weighted BCE + CORAL loss ----------------
+ * Replace FusionModule.py:341-390 (_compute_loss, shared by OnlyImagingModule) and
+ * coral_loss/coral.py:5-37 with one device op in fp64 that returns the three logged losses and
+ * both gradients: no boolean-mask index, nothing read back.  With x_i row i of feat, c_i =
+ * domain[i] (0 INTERNAL / source, 1 BTXRD / target, anything else takes no part in CORAL but counts
+ * in the BCE), n_s, n_t the two counts, mu_s, mu_t the domains' column means and
+ * w_i = +1 / (n_s - 1) (source), -1 / (n_t - 1) (target), 0 (else):
+ *   Delta = sum_i w_i x_i x_i^T - mu_s mu_s^T / (n_s - 1) + mu_t mu_t^T / (n_t - 1)      [D][D]
+ *   coral = lambda ||Delta||_F^2 / (4 D^2)
+ *   d coral / d x_i = (lambda w_i / D^2) (x_i - mu_dom(i) / n_dom(i)) Delta
+ * -- the reference's "covariance" subtracts the mean outer product once, not n times
+ * (coral.py:31-35), which is kept.  coral and its gradient are exactly 0 where n_s <= 1, n_t <= 1 or
+ * lambda == 0 (:375-376); the device decides that from the codes.  With z_i = logits[i], y_i =
+ * label[i] and u_i = w0 where y_i == 0, else w1:
+ *   cls = (1 / N) sum_i u_i (max(z_i, 0) - z_i y_i + log1p(exp(-|z_i|)))
+ *   d cls / d z_i = u_i (sigmoid(z_i) - y_i) / N
+ * out[3] (fp64, written on the device) = { cls + coral, cls, coral }; g_feat [N][D] fp32 =
+ * d coral / d x and g_logits [N] fp32 = d cls / d z, each rounded once from fp64.  A NULL g_feat
+ * skips the gradient pass (and Delta's store), a NULL g_logits that store; out's bits do not
+ * depend on either.  feat [N][ldf] fp32; label_kind as vlp_binmetric_append (0 int64, 1 int32,
+ * 2 uint8); ws: vlp_domain_loss_ws_bytes(N, D) bytes of scratch that need no initialisation.
+ *
+ * At most four launches (three without g_feat, two at lambda == 0 without it): the statistics
+ * (per chunk of 256 rows: per-domain column sums, counts, the BCE sum, g_logits), the 64 x 64
+ * tiles of Delta with their Frobenius partials, the 32 x 64 tiles of g_feat, and a one-workgroup
+ * fold into out.  fp64 FMA throughout, no atomics; every sum runs in one order fixed by N and D
+ * (rows in ascending index, Delta's rows in ascending index, partials thread-strided and then a
+ * halving tree), so two calls on the same inputs return the same bits.
+ * hipErrorInvalidValue before any launch: a NULL pointer that the call uses (out always; feat,
+ * logits, label, domain, ws when N > 0), N < 0, N > 2^18, D < 1, D > 2048, ldf < D, a label_kind
+ * outside 0 .. 2, ws_bytes below vlp_domain_loss_ws_bytes.  N = 0 launches nothing and zeroes out. */
+int vlp_domain_loss_ws_bytes(int N, int D, long long* bytes);
+int vlp_domain_loss(int N, int D, const float* feat, long long ldf, const float* logits, const void* label,
+                    int label_kind, const unsigned char* domain, double w0, double w1, double coral_lambda,
+                    double* out, float* g_feat, float* g_logits, double* ws, long long ws_bytes, void* stream);
+
 /* ---------------- NesT image encoder (BASELINE configs[3]) ----------------
  * Replace timm nest.py's pieces behind ImageEncoder's timm.create_model("nest_small", ...)
  * (VisionLanguageModule.py:27-35).  Blocked local attention: qkv[BT*N][3C] rows (q | k | v,

@@ -1,7 +1,8 @@
 """Late-fusion finetune step (BASELINE configs[4]: ResNet34 Imaging+Clinical, bs=512,
 512x512, bf16) on the HIP ResNet34 tower: images/s for forward + backward + AdamW.
 
-    python tools/fusion_bench.py [--batch 512] [--steps 10] [--warmup 3] [--out F]
+    python tools/fusion_bench.py [--batch 512] [--steps 10] [--warmup 3] [--coral-lambda L]
+                                 [--loss-on-device] [--out F]
 
 One process per GPU; under torch.distributed.run each rank takes its own bs and the
 gradients are SUM-all-reduced (one RCCL call over the tower's flat gradient arena,
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--coral-lambda", type=float, default=0.5)
+    ap.add_argument("--loss-on-device", action="store_true",
+                    help="the weighted BCE + CORAL loss as one fp64 device op (FusionModule loss_on_device)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -45,7 +48,8 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(0)
     m = FusionModule("resnet34", functools.partial(torch.optim.AdamW, lr=1e-4, fused=True),
-                     label_weights=(0.6, 1.8), coral_lambda=a.coral_lambda, compute_dtype="bf16")
+                     label_weights=(0.6, 1.8), coral_lambda=a.coral_lambda, compute_dtype="bf16",
+                     loss_on_device=a.loss_on_device)
     opt = m.configure_optimizers()["optimizer"]
     B, H = a.batch, a.image_size
     g = torch.Generator().manual_seed(1 + rank)
@@ -93,7 +97,7 @@ def main():
            "value": round(ips, 2), "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": round(el / a.steps * 1e3, 3), "dtype": "bf16", "data": "synthetic",
            "config": {"workload": "BASELINE configs[4] FusionModule resnet34", "per_gpu_batch": B,
-                      "image_size": H, "coral_lambda": a.coral_lambda},
+                      "image_size": H, "coral_lambda": a.coral_lambda, "loss_on_device": a.loss_on_device},
            "model_flops_frac": round(ips * GFLOP_PER_IMAGE * 1e9 / (world * 2.5e15), 4),
            "loss": round(loss.item(), 5)}
     if rank == 0:

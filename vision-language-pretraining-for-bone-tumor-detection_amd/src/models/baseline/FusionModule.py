@@ -25,7 +25,11 @@ directly, so forward_features returns them as [B, 512, 1, 1]: the reference's
 consumers only take the spatial mean of that map (forward_head's global pool,
 CORAL's mean over (2, 3), :366-369), which is the identity on a 1x1 map.  The
 fc, the 15->32->20->10 tabular MLP with BatchNorm1d, the 20->1 combination and
-the loss (a few kFLOP per sample) run as device tensor ops.
+the loss (a few kFLOP per sample) run as device tensor ops.  With
+`loss_on_device=True` the loss (weighted BCE + CORAL, both gradients) is one fp64
+device op instead (vlp_amd/domain_loss.py, csrc/domain_loss_ops.hip): the training
+step and the epoch-end combined loss make no boolean-mask index and no
+device-to-host read; the default path is unchanged.
 
 Not built: the vit / resnet50 / nest_small / torchxrayvision backbones
 (NotImplementedError).  The t-SNE of the image features is part
@@ -51,6 +55,7 @@ if _PKG not in sys.path:
 from src.models.pretrain.VisionLanguageModule import (VisionLanguageModule, _Base, _HAVE_LIGHTNING,  # noqa: E402
                                                        _default_device)
 from src.utils.coral_loss.coral import coral  # noqa: E402
+from vlp_amd.domain_loss import domain_loss  # noqa: E402
 from vlp_amd.metrics import BinaryMetricsDevice  # noqa: E402
 from vlp_amd.resnet34 import ResNet34Tower  # noqa: E402
 
@@ -94,12 +99,14 @@ class FusionModule(_Base):
         vision_encoder_lr: float = None,
         compute_dtype: str = "fp32",
         device=None,
+        loss_on_device: bool = False,
         **kwargs,
     ):
         super().__init__()
         hp = dict(model=model, optimizer=optimizer, scheduler=scheduler, label_weights=label_weights,
                   coral_lambda=coral_lambda, pretrained_vlp_module=pretrained_vlp_module,
-                  vision_encoder_lr=vision_encoder_lr, compute_dtype=compute_dtype, **kwargs)
+                  vision_encoder_lr=vision_encoder_lr, compute_dtype=compute_dtype,
+                  loss_on_device=loss_on_device, **kwargs)
         if _HAVE_LIGHTNING:  # pragma: no cover
             self.save_hyperparameters(logger=False)
         else:
@@ -212,6 +219,11 @@ class FusionModule(_Base):
         return self.image_network.forward_head(x)
 
     def _compute_loss(self, image_features, logits, labels, dataset):
+        if getattr(self.hparams, "loss_on_device", False) and image_features.is_cuda:
+            # one fp64 device op (csrc/domain_loss_ops.hip): no mask index, no read-back, and the
+            # :375-376 rule below decided on the device from the rows' domain codes
+            return domain_loss(image_features, logits, labels, dataset, self.label_weights,
+                               self.hparams.coral_lambda)
         labels = labels.to(logits.device)
         lw = self.label_weights.to(logits.device)
         sample_weights = torch.where(labels == 0, lw[0], lw[1])

@@ -36,6 +36,11 @@ vlp_amd.metrics.BinaryMetricsDevice instead: the epoch's probabilities and label
 stay on the device, a step adds one launch and no device-to-host copy, and each
 set of five values costs one 48-byte read at the end of the epoch; both return
 the same bits (the shared binary_metrics_from_counts).
+
+Loss: with `loss_on_device=True` _compute_loss (shared with FusionModule) is one fp64
+device op for the weighted BCE, the CORAL term and both gradients
+(vlp_amd/domain_loss.py): no boolean-mask index and no device-to-host read in the
+training step or the epoch-end combined loss.  The default path is unchanged.
 """
 from __future__ import annotations
 
@@ -148,13 +153,14 @@ class OnlyImagingModule(_Base):
         image_size: int = 224,
         device=None,
         metrics_on_device: bool = False,
+        loss_on_device: bool = False,
         **kwargs,
     ):
         super().__init__()
         hp = dict(model=model, optimizer=optimizer, scheduler=scheduler, label_weights=label_weights,
                   coral_lambda=coral_lambda, pretrained_vlp_module=pretrained_vlp_module,
                   compute_dtype=compute_dtype, image_size=image_size, metrics_on_device=metrics_on_device,
-                  **kwargs)
+                  loss_on_device=loss_on_device, **kwargs)
         if _HAVE_LIGHTNING:  # pragma: no cover
             self.save_hyperparameters(logger=False)
         else:

@@ -926,6 +926,48 @@ def binmetric_counts(n, scores, labels, counts):
     return out
 
 
+# ---------------- the baselines' weighted BCE + CORAL loss ----------------
+DOMAIN_LOSS_MAX_N = 1 << 18   # kDlMaxN of csrc/domain_loss_ops.hip
+DOMAIN_LOSS_MAX_D = 2048      # kDlMaxD
+
+
+def domain_loss_ws_bytes(N, D):
+    n = ctypes.c_longlong(0)
+    lib().vlp_domain_loss_ws_bytes(int(N), int(D), ctypes.byref(n))
+    return n.value
+
+
+def domain_loss(feat, logits, label, domain, w0, w1, coral_lambda, grad=True):
+    """(out, g_feat, g_logits) of vlp_domain_loss: out [3] fp64 = total, cls, coral on the device,
+    g_feat [N, D] fp32 = d coral / d feat and g_logits [N] fp32 = d cls / d logits (both None when
+    grad is false: the gradient pass is skipped).  feat [N, D] fp32 (any row stride >= D, unit
+    column stride); logits [N] fp32; label [N] int64, int32, uint8 or bool; domain [N] uint8 codes
+    (0 source, 1 target, else neither).  Nothing is read back."""
+    N, D = feat.shape
+    if not (0 <= N <= DOMAIN_LOSS_MAX_N and 1 <= D <= DOMAIN_LOSS_MAX_D):
+        raise ValueError(f"domain_loss: N={N}, D={D}; 0 to {DOMAIN_LOSS_MAX_N} rows and 1 to "
+                         f"{DOMAIN_LOSS_MAX_D} columns")
+    if label.dtype == torch.bool:
+        label = label.view(torch.uint8)
+    if label.dtype not in _BINMETRIC_KIND:
+        raise TypeError(f"domain_loss: labels must be int64, int32, uint8 or bool, got {label.dtype}")
+    assert feat.dtype == torch.float32 and feat.stride(1) == 1 and (N <= 1 or feat.stride(0) >= D)
+    assert logits.dtype == torch.float32 and logits.shape == (N,) and logits.is_contiguous()
+    assert label.shape == (N,) and label.is_contiguous()
+    assert domain.dtype == torch.uint8 and domain.shape == (N,) and domain.is_contiguous()
+    dev = feat.device
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    g_feat = torch.empty(N, D, dtype=torch.float32, device=dev) if grad else None
+    g_logits = torch.empty(N, dtype=torch.float32, device=dev) if grad else None
+    nbytes = domain_loss_ws_bytes(N, D)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    ldf = feat.stride(0) if N > 1 else D
+    lib().vlp_domain_loss(N, D, ptr(feat), ldf, ptr(logits), ptr(label), _BINMETRIC_KIND[label.dtype], ptr(domain),
+                          float(w0), float(w1), float(coral_lambda), ptr(out), ptr(g_feat), ptr(g_logits), ptr(ws),
+                          nbytes, _s())
+    return out, g_feat, g_logits
+
+
 # ---------------- NesT image encoder (SURVEY §8(f) row 2) ----------------
 def nest_attn_fwd(qkv, out, lse, BT, H, N, scale):
     tk = ktimer.begin("nest_attn_fwd", 4.0 * BT * H * N * N * 32)
