@@ -533,6 +533,33 @@ int vlp_binmetric_pairs(int n, const float* scores, const unsigned char* labels,
 int vlp_binmetric_fold(int nparts, const unsigned long long* parts, const long long* counts, long long* out,
                        void* stream);
 
+/* ---------------- the test-set evaluation's per-subgroup counts ----------------
+ * Replace the boolean-mask subsets of scripts/test_eval_downstream.py:120-236 (evaluate_results:
+ * about 40 subsets per fold, six sklearn calls each) with one device op that counts every group of
+ * every level at once.  n rows: scores [n] fp32 (probabilities: finite, a NaN is out of contract as
+ * above), labels [n] uint8 in vlp_binmetric_append's encoding (1, 0, or 2 = counted nowhere), and
+ * for each of L levels (1 .. 8) a group code per row, codes [L][n] uint8: 0 .. G_l - 1, or 255 for
+ * "in no group of this level".  cell_base [L + 1] (HOST memory) holds the prefix sums of the G_l
+ * (1 .. 255 each, cell_base[0] = 0); cells = cell_base[L].
+ *   out [cells][6] int64: for level l and group g, at cell_base[l] + g, over the rows with
+ *   codes[l][.] == g: tp, fp, fn, tn with the prediction score >= 0.5f, and over positive i and
+ *   negative j among them wins = #{s_i > s_j}, ties = #{s_i == s_j}
+ * -- vlp_binmetric_*'s six integers for that subset; a level with G = 1 and all codes 0 returns
+ * exactly what they return.  A pair belongs to a level's group when both rows carry its code, so
+ * one pass over the pairs serves all levels.  Two launches: the pair kernel on a grid
+ * (ceil(n / 256), splits) -- 256 rows i in registers with their codes packed in 64 bits, the j
+ * range streamed through LDS as (score or NaN, packed codes), per pair two fp32 compares and per
+ * level a byte compare and two 32-bit adds; each workgroup folds its threads by cell through LDS
+ * and writes its own [cells][6] partial into ws -- and a one-workgroup fold.  Integers only, no
+ * atomics, bitwise reproducible.  ws: vlp_groupmetric_ws_bytes(n, L, cells) bytes of scratch that
+ * need no initialisation.  hipErrorInvalidValue before any launch: a NULL pointer, n < 1,
+ * n > 2^18, L outside 1 .. 8, cell_base[0] != 0, a G_l outside 1 .. 255 (a cell_base that does not
+ * increase), ws_bytes below vlp_groupmetric_ws_bytes. */
+int vlp_groupmetric_ws_bytes(int n, int L, int cells, long long* bytes);
+int vlp_groupmetric_counts(int n, const float* scores, const unsigned char* labels, int L,
+                           const unsigned char* codes, const int* cell_base, long long* out, void* ws,
+                           long long ws_bytes, void* stream);
+
 /* ---------------- the baselines' weighted BCE + CORAL loss ----------------
  * Replace FusionModule.py:341-390 (_compute_loss, shared by OnlyImagingModule) and
  * coral_loss/coral.py:5-37 with one device op in fp64 that returns the three logged losses and

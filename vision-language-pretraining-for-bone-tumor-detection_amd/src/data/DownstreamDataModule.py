@@ -10,6 +10,9 @@ batch keys FusionModule reads: "x-ray", "tumor", "dataset", "anatomy_site_encode
 [B,9], "age_encoded" [B,4], "sex_encoded" [B,2] (FusionModule.py:392-394).
 MI355X: the image goes up as the uint8 1-channel "x-ray-u8" by default (normalised
 on the device), upload="fp32" gives the normalised 3-channel "x-ray".
+test_dataloader(fold) (:340-383) concatenates the INTERNAL and the BTXRD test sets, unshuffled;
+its batches also carry the metadata the evaluation scripts group by ("entity",
+"anatomy_site", "sex", "age"); the train and validation batches do not.
 The BTXRD / INTERNAL readers and MONAI transforms are not built (no data in this
 image): synthetic=False raises NotImplementedError.
 """
@@ -18,7 +21,7 @@ from __future__ import annotations
 from typing import List, Optional
 
 import torch
-from torch.utils.data import DataLoader, Dataset, Subset
+from torch.utils.data import ConcatDataset, DataLoader, Dataset, Subset
 
 from src.data.PretrainDataModule import normalize_u8
 
@@ -48,6 +51,55 @@ class SyntheticClinicalRadiographs(Dataset):
         }
 
 
+# the test set's metadata vocabularies (the strings the evaluation scripts group by)
+ANATOMY_SITES = ("shoulder", "upper arm", "elbow", "lower arm", "hand", "hip", "upper leg", "knee", "lower leg")
+SEXES = ("M", "F")                     # sex_encoded index 0 / 1
+AGE_EDGES = (19, 40, 60)               # age_encoded index = number of edges <= age
+# (entity, probability of tumor = 1): most entities decide the label, as in the real data
+ENTITIES = (("undefined", 0.0), ("osteochondroma", 1.0), ("enchondroma", 1.0), ("osteosarcoma", 1.0),
+            ("giant cell tumor", 1.0), ("other", 0.5))
+_ENTITY_WEIGHTS = (0.45, 0.1, 0.1, 0.1, 0.05, 0.2)
+assert len(ANATOMY_SITES) == N_SITES and len(SEXES) == N_SEX and len(AGE_EDGES) + 1 == N_AGE
+
+
+class SyntheticClinicalTestRadiographs(Dataset):
+    """The held-out test set of one source dataset (`dataset` = "INTERNAL" or "BTXRD"): the keys
+    of SyntheticClinicalRadiographs plus what the evaluation scripts read -- "entity" (a string,
+    drawn first; it decides "tumor" except for "other"), "anatomy_site", "sex", "age" (integer
+    years), each consistent with its one-hot encoding."""
+
+    def __init__(self, n: int, image_size: int, seed: int = 0, dataset: str = "INTERNAL"):
+        self.n, self.H, self.seed, self.dataset = n, image_size, seed, dataset
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        g = torch.Generator().manual_seed(self.seed * 1_000_003 + i)
+        oh = torch.nn.functional.one_hot
+        entity, rate = ENTITIES[int(torch.multinomial(torch.tensor(_ENTITY_WEIGHTS), 1, generator=g))]
+        tumor = int(torch.rand((), generator=g) < rate)
+        site = int(torch.randint(0, N_SITES, (), generator=g))
+        sex = int(torch.randint(0, N_SEX, (), generator=g))
+        age = int(torch.randint(1, 90, (), generator=g))
+        age_bin = sum(age >= e for e in AGE_EDGES)
+        return {
+            "x-ray-u8": torch.randint(0, 256, (1, self.H, self.H), generator=g, dtype=torch.uint8),
+            "tumor": tumor,
+            "dataset": self.dataset,
+            "anatomy_site_encoded": oh(torch.tensor(site), N_SITES).float(),
+            "age_encoded": oh(torch.tensor(age_bin), N_AGE).float(),
+            "sex_encoded": oh(torch.tensor(sex), N_SEX).float(),
+            "image_path": f"synthetic://downstream/test/{self.dataset}/{i}.png",
+            "entity": entity,
+            "anatomy_site": ANATOMY_SITES[site],
+            "sex": SEXES[sex],
+            "age": age,
+        }
+
+
 class ClinicalCollator:
     def __init__(self, upload: str = "u8", num_channels: int = 3):
         if upload not in ("u8", "fp32"):
@@ -62,6 +114,11 @@ class ClinicalCollator:
              "dataset": [s["dataset"] for s in samples], "image_path": [s["image_path"] for s in samples]}
         for k in ("anatomy_site_encoded", "age_encoded", "sex_encoded"):
             b[k] = torch.stack([s[k] for s in samples])
+        for k in ("entity", "anatomy_site", "sex"):     # the test set's metadata: passed through
+            if k in samples[0]:
+                b[k] = [s[k] for s in samples]
+        if "age" in samples[0]:
+            b["age"] = torch.tensor([s["age"] for s in samples], dtype=torch.long)
         if self.upload == "u8":
             b["x-ray-u8"] = x_u8
         else:
@@ -87,7 +144,8 @@ class DownstreamDataModule:
                  num_channels: int = 3, try_with_only_n_samples: Optional[int] = None,
                  gaussian_noise_augmentation: bool = True, scale_intensity_normalization: bool = False,
                  synthetic: bool = True, image_size: int = 224, n_samples: int = 512,
-                 n_val_samples: int = 64, n_folds: int = 1, upload: str = "u8", seed: int = 0):
+                 n_val_samples: int = 64, n_folds: int = 1, upload: str = "u8", seed: int = 0,
+                 n_test_samples: int = 128):
         if not (num_channels == 1 or num_channels == 3):
             raise ValueError(f"DownstreamDataModule: num_channels must be 1 or 3, but got {num_channels}")
         if not synthetic:
@@ -99,6 +157,7 @@ class DownstreamDataModule:
         self.num_channels, self.try_with_only_n_samples = num_channels, try_with_only_n_samples
         self.image_size, self.n_samples, self.n_val, self.n_folds, self.seed = (
             image_size, n_samples, n_val_samples, n_folds, seed)
+        self.n_test = n_test_samples
         self.collate = ClinicalCollator(upload if num_channels == 3 else "fp32", num_channels)
 
     @staticmethod
@@ -141,3 +200,18 @@ class DownstreamDataModule:
             w1 = len(labels) / (2 * n1) if n1 else float("inf")
             yield DataModuleFolds(self._loader(train, True), [self._loader(v, False) for v in vals],
                                   self.batch_size), (float(w0), float(w1))
+
+    def test_dataloader(self, fold: int) -> DataLoader:
+        """The held-out test loader of `fold` (reference :340-383): the INTERNAL and the BTXRD
+        test sets concatenated, in order (shuffle=False), each capped at try_with_only_n_samples
+        when that is set; the module's collator and upload mode.  `fold` selects the seed as
+        get_cv_splits does (the reference's fold selects the normalisation statistics).  The
+        batches carry the evaluation scripts' metadata: "entity", "anatomy_site", "sex", "age"."""
+        if not 0 <= fold:
+            raise ValueError(f"DownstreamDataModule.test_dataloader: fold must be >= 0, got {fold}")
+        n = self.n_test if self.try_with_only_n_samples is None else min(self.n_test, self.try_with_only_n_samples)
+        sets = [SyntheticClinicalTestRadiographs(n, self.image_size, self.seed + 101 * fold + 11 + k, name)
+                for k, name in enumerate(("INTERNAL", "BTXRD"))]
+        return DataLoader(ConcatDataset(sets), batch_size=self.batch_size, shuffle=False,
+                          num_workers=self.num_workers, collate_fn=self.collate,
+                          pin_memory=torch.cuda.is_available())

@@ -68,7 +68,7 @@ _FAMILY_TIMED = {"vlp_conv_fwd", "vlp_conv_fwd_act", "vlp_conv_dgrad", "vlp_conv
 # host-side queries (no GPU work): never timed
 _QUERIES = {"vlp_linear_wgrad_ws_floats", "vlp_clip_loss_ws_floats", "vlp_stem1_bwd_fused_ws_floats",
             "vlp_stem1_fused_ok", "vlp_conv_fwd_act_ok", "vlp_conv_dgrad_act_ok", "vlp_grad_sumsq_nparts",
-            "vlp_domain_loss_ws_bytes"}
+            "vlp_domain_loss_ws_bytes", "vlp_groupmetric_ws_bytes"}
 
 
 class HipError(RuntimeError):

@@ -27,6 +27,12 @@ BinaryMetricsDevice is the baselines' epoch accumulator for accuracy, precision,
 recall, F1 and AUROC with its state on the device (csrc/binmetric_ops.hip: integer
 counts, one 48-byte read per compute()); binary_metrics_from_counts is the host
 arithmetic it shares with OnlyImagingModule's binary_metrics.
+
+grouped_binary_counts and subgroup_metrics_from_counts are the test-set evaluation
+(reference scripts/test_eval_downstream.py: six sklearn metrics overall and per
+dataset, entity, anatomy site, sex and age group): the same six integers for every
+group of every level from one pass over the pairs (csrc/groupmetric_ops.hip), and
+the script's own one-class rules on the host.
 """
 from __future__ import annotations
 
@@ -651,3 +657,86 @@ class BinaryMetricsDevice:
             return out
         tp, fp, fn, tn, wins, ties = self.counts()
         return binary_metrics_from_counts(tp, fp, fn, tn, 2 * wins + ties)
+
+
+# ---------------- the test-set evaluation's per-subgroup metrics ----------------
+NO_GROUP = 255   # kGmMaxGroups of csrc/groupmetric_ops.hip: the code of a row in no group of a level
+SUBGROUP_METRICS = ("accuracy", "balanced_accuracy", "roc_auc", "precision", "recall", "f1_score")
+
+
+def _labels_u8(labels: torch.Tensor) -> torch.Tensor:
+    """vlp_binmetric_append's encoding: 1 where the label is 1, 0 where it is 0, else 2."""
+    if labels.dtype == torch.uint8:
+        return labels
+    one, two = torch.ones_like(labels), torch.full_like(labels, 2)
+    return torch.where(labels == 1, one, torch.where(labels == 0, torch.zeros_like(labels), two)).to(torch.uint8)
+
+
+def grouped_binary_counts(scores: torch.Tensor, labels: torch.Tensor, codes: torch.Tensor,
+                          n_groups: Sequence[int]) -> torch.Tensor:
+    """int64 [cells, 6] on the scores' device: tp, fp, fn, tn, wins, ties -- BinaryMetricsDevice's
+    six integers -- of every group of every level.  scores [n] (taken as fp32), labels [n] (0 or 1;
+    any other value, and 2 in a uint8 tensor, is counted nowhere), codes [L, n] uint8 with row i's
+    group in level l (0 .. n_groups[l] - 1, or NO_GROUP = 255 for none), 1 <= L <= 8 levels of at
+    most 255 groups.  Level l's group g is row sum(n_groups[:l]) + g of the result; a declared
+    group that no row carries is a row of zeros.
+
+    On device tensors one pass over the pairs counts all levels (csrc/groupmetric_ops.hip: two
+    launches, integers only, bitwise reproducible) and nothing is read back -- the caller's
+    .tolist() is the one read of cells x 48 bytes.  On CPU tensors every level and group takes its
+    boolean mask, the four threshold counts and binary_pair_counts_cpu, in plain torch: the
+    reference the device is held to, bit for bit.  ValueError before any launch for L outside
+    1 .. 8, a group count outside 1 .. 255 or lengths that do not match."""
+    from . import ops
+    n, L, cell_base = ops.groupmetric_check(scores, labels, codes, n_groups)
+    if codes.dtype != torch.uint8:
+        raise TypeError(f"grouped_binary_counts: codes must be uint8, got {codes.dtype}")
+    s = scores.detach()
+    if s.dtype != torch.float32:
+        s = s.float()
+    y = _labels_u8(labels.detach().to(s.device))
+    codes = codes.to(s.device)
+    if s.is_cuda:
+        return ops.groupmetric_counts(s.contiguous(), y.contiguous(), codes.contiguous(), n_groups)
+    out = torch.zeros(cell_base[-1], 6, dtype=torch.int64)
+    pred, pos, neg = s >= 0.5, y == 1, y == 0
+    for l in range(L):
+        for g in range(cell_base[l + 1] - cell_base[l]):
+            m = codes[l] == g
+            wins, ties = binary_pair_counts_cpu(s[m], y[m])
+            out[cell_base[l] + g] = torch.tensor([int((m & pred & pos).sum()), int((m & pred & neg).sum()),
+                                                  int((m & ~pred & pos).sum()), int((m & ~pred & neg).sum()),
+                                                  wins, ties])
+    return out
+
+
+def subgroup_metrics_from_counts(tp, fp, fn, tn, u2) -> dict:
+    """The six values of the reference's calculate_metrics (scripts/test_eval_downstream.py:244-278:
+    sklearn's accuracy_score, balanced_accuracy_score, roc_auc_score, precision_score, recall_score,
+    f1_score at a 0.5 threshold) from the confusion counts and u2 = 2 wins + ties, in the script's
+    key order.  These are the script's rules, not binary_metrics_from_counts':
+      accuracy           (tp + tn) / n
+      balanced_accuracy  the mean of the recalls of the classes present in the labels (sklearn drops
+                         an absent class), so a one-class group gives that class's recall
+      with fewer than two classes present roc_auc, precision, recall and f1_score are NaN
+      roc_auc            u2 / (2 n1 n0)
+      precision          tp / (tp + fp), 0.0 when nothing is predicted positive (sklearn's zero_division)
+      recall             tp / (tp + fn)
+      f1_score           2 tp / (2 tp + fp + fn), 0.0 on a zero denominator
+    Every quotient is one fp64 division of exact integers.  An empty group is NaN throughout."""
+    nan = float("nan")
+    n1, n0 = tp + fn, fp + tn
+    n = n1 + n0
+    if n == 0:
+        return dict.fromkeys(SUBGROUP_METRICS, nan)
+    out = {"accuracy": (tp + tn) / n}
+    if n1 and n0:
+        out["balanced_accuracy"] = (tp / n1 + tn / n0) / 2
+        out["roc_auc"] = float(u2 / (2 * n1 * n0))
+        out["precision"] = tp / (tp + fp) if tp + fp else 0.0
+        out["recall"] = tp / n1
+        out["f1_score"] = 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0
+    else:
+        out["balanced_accuracy"] = tp / n1 if n1 else tn / n0
+        out.update(roc_auc=nan, precision=nan, recall=nan, f1_score=nan)
+    return out

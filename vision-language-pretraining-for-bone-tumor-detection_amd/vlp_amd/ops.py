@@ -926,6 +926,65 @@ def binmetric_counts(n, scores, labels, counts):
     return out
 
 
+# ---------------- the test-set evaluation's per-subgroup counts ----------------
+GROUPMETRIC_MAX_LEVELS = 8     # kGmMaxLevels of csrc/groupmetric_ops.hip: one byte per level in 64 bits
+GROUPMETRIC_MAX_GROUPS = 255   # kGmMaxGroups: codes 0 .. 254
+GROUPMETRIC_NO_GROUP = 255     # the code of a row that is in no group of a level
+
+
+def groupmetric_check(scores, labels, codes, n_groups):
+    """(n, L, cell_base) of a grouped count's arguments; ValueError on shapes or sizes the op does
+    not take.  Nothing but the tensors' shapes is read: no library call, no device access."""
+    n_groups = [int(g) for g in n_groups]
+    L = len(n_groups)
+    if not 1 <= L <= GROUPMETRIC_MAX_LEVELS:
+        raise ValueError(f"groupmetric: {L} levels; 1 to {GROUPMETRIC_MAX_LEVELS} are supported")
+    for l, g in enumerate(n_groups):
+        if not 1 <= g <= GROUPMETRIC_MAX_GROUPS:
+            raise ValueError(f"groupmetric: level {l} declares {g} groups; 1 to {GROUPMETRIC_MAX_GROUPS} are "
+                             f"supported")
+    if scores.dim() != 1 or labels.dim() != 1 or codes.dim() != 2:
+        raise ValueError(f"groupmetric: scores [n], labels [n] and codes [L, n], got {tuple(scores.shape)}, "
+                         f"{tuple(labels.shape)} and {tuple(codes.shape)}")
+    n = scores.shape[0]
+    if labels.shape[0] != n or codes.shape[1] != n or codes.shape[0] != L:
+        raise ValueError(f"groupmetric: {n} scores, {labels.shape[0]} labels, codes {tuple(codes.shape)} and "
+                         f"{L} group counts do not match")
+    if not 1 <= n <= BINMETRIC_MAX_N:
+        raise ValueError(f"groupmetric: n={n}; the pair count takes 1 to {BINMETRIC_MAX_N} rows")
+    cell_base = [0]
+    for g in n_groups:
+        cell_base.append(cell_base[-1] + g)
+    return n, L, cell_base
+
+
+def groupmetric_ws_bytes(n, L, cells):
+    b = ctypes.c_longlong(0)
+    lib().vlp_groupmetric_ws_bytes(int(n), int(L), int(cells), ctypes.byref(b))
+    return b.value
+
+
+def groupmetric_counts(scores, labels, codes, n_groups):
+    """int64 [cells, 6] on the device: tp, fp, fn, tn, wins, ties of every group of every level
+    (vlp_groupmetric_counts: two launches, nothing read back).  scores [n] fp32; labels [n] uint8 (1,
+    0, or 2 = counted nowhere); codes [L, n] uint8, row i's group per level or 255 for none;
+    n_groups the levels' group counts.  Level l's group g is row sum(n_groups[:l]) + g."""
+    n, L, cell_base = groupmetric_check(scores, labels, codes, n_groups)
+    if scores.dtype != torch.float32 or labels.dtype != torch.uint8 or codes.dtype != torch.uint8:
+        raise TypeError(f"groupmetric_counts: scores fp32, labels uint8 and codes uint8, got {scores.dtype}, "
+                        f"{labels.dtype} and {codes.dtype}")
+    assert scores.is_contiguous() and labels.is_contiguous() and codes.is_contiguous()
+    assert labels.device == scores.device and codes.device == scores.device
+    cells = cell_base[-1]
+    out = torch.empty(cells, 6, dtype=torch.int64, device=scores.device)
+    nbytes = groupmetric_ws_bytes(n, L, cells)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=scores.device)
+    base = (ctypes.c_int * (L + 1))(*cell_base)
+    lib().vlp_groupmetric_counts(n, ptr(scores), ptr(labels), L, ptr(codes), ctypes.cast(base, ctypes.c_void_p),
+                                 ptr(out), ptr(ws), nbytes, _s())
+    return out
+
+
 # ---------------- the baselines' weighted BCE + CORAL loss ----------------
 DOMAIN_LOSS_MAX_N = 1 << 18   # kDlMaxN of csrc/domain_loss_ops.hip
 DOMAIN_LOSS_MAX_D = 2048      # kDlMaxD
