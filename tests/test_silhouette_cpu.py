@@ -138,6 +138,10 @@ class _StandIn(torch.nn.Module):
     def forward_head(self, f):
         return self.scale * (torch.round(f.mean((2, 3))[:, 0] * 255.0) - 128.0)
 
+    def features_and_logits(self, batch):
+        f = self.forward_features(self._unpack(batch)[0])
+        return f, self.forward_head(f)
+
     @classmethod
     def load_from_checkpoint(cls, path, device=None):
         m = cls(device=device)

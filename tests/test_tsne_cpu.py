@@ -222,6 +222,10 @@ def test_evaluate_split_tsne_and_files(tmp_path, monkeypatch):
         def forward_head(self, f):
             return f.sum(1)
 
+        def features_and_logits(self, batch):
+            f = self.forward_features(self._unpack(batch)[0])
+            return f, self.forward_head(f)
+
     g = torch.Generator().manual_seed(0)
     batches = [{"x": torch.randn(6, 6, generator=g) + 3 * (b % 2), "tumor": torch.tensor([0, 1, 0, 1, 1, 0]),
                 "dataset": ["INTERNAL", "BTXRD"] * 3} for b in range(2)]

@@ -94,6 +94,23 @@ def _default_device(device):
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def load_lightning_checkpoint(cls, checkpoint_path, map_location=None, strict=True, **kwargs):
+    """`cls.load_from_checkpoint` of the three training modules: a Lightning-format checkpoint
+    ({"state_dict", "hyper_parameters"}); loaded with weights_only=True (hyper-parameters
+    holding objects must be passed again as kwargs, as src/train.py:198 does for the
+    datamodule)."""
+    from src.utils.config import instantiate
+    ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+    hp = dict(ckpt.get("hyper_parameters", {}))
+    # factories saved as {_target_, _partial_} nodes (src/utils/trainer.serializable_hparams)
+    hp = {k: instantiate(v) if isinstance(v, dict) and "_target_" in v else v for k, v in hp.items()}
+    hp.pop("num_optimized_params", None)
+    hp.update(kwargs)
+    model = cls(**hp)
+    model.load_state_dict(ckpt["state_dict"], strict=strict)
+    return model
+
+
 class ImageEncoder(nn.Module):
     """:27-35 — `timm.create_model(model, pretrained=False, num_classes=0,
     global_pool="avg", **kwargs)`; here the MI355X ResNet34, NesT or ViT tower."""
@@ -656,16 +673,4 @@ class VisionLanguageModule(_Base):
     # ---------------- checkpoints ----------------
     @classmethod
     def load_from_checkpoint(cls, checkpoint_path, map_location=None, strict=True, **kwargs):
-        """Lightning-format checkpoint ({"state_dict", "hyper_parameters"}); loaded
-        with weights_only=True (hyper-parameters holding objects must be passed
-        again as kwargs, as src/train.py:198 does for the datamodule)."""
-        from src.utils.config import instantiate
-        ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
-        hp = dict(ckpt.get("hyper_parameters", {}))
-        # factories saved as {_target_, _partial_} nodes (src/utils/trainer.serializable_hparams)
-        hp = {k: instantiate(v) if isinstance(v, dict) and "_target_" in v else v for k, v in hp.items()}
-        hp.pop("num_optimized_params", None)
-        hp.update(kwargs)
-        model = cls(**hp)
-        model.load_state_dict(ckpt["state_dict"], strict=strict)
-        return model
+        return load_lightning_checkpoint(cls, checkpoint_path, map_location, strict, **kwargs)

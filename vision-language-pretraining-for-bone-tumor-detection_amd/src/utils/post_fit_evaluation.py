@@ -51,14 +51,7 @@ def best_checkpoint_callback(trainer):
 
 def _features_and_logits(model, batch):
     """One pass: (features [B, F] or [B, F, h, w], logits [B])."""
-    from src.models.baseline.FusionModule import FusionModule
-    if isinstance(model, FusionModule):
-        x, _, _, site, age, sex = model._unpack(batch)
-        logits, features = model(x, age, sex, site)
-        return features, logits
-    x = model._unpack(batch)[0]
-    features = model.forward_features(x)
-    return features, model.forward_head(features)
+    return model.features_and_logits(batch)
 
 
 def evaluate_split(model, dataloaders, tsne: bool = False) -> Dict[str, Any]:

@@ -158,17 +158,10 @@ def predictions_from_table(columns: dict, probs: torch.Tensor) -> Predictions:
 
 
 def collect_probs(model, dataloader) -> Predictions:
-    """sigmoid(logits) of `model` (an OnlyImagingModule, called on the image, or a FusionModule,
-    called on the image and the three encodings) over a test dataloader: eval mode, no_grad."""
-    from src.models.baseline.FusionModule import FusionModule
-
+    """sigmoid(logits) of `model` (a BaselineModule: its features_and_logits(batch)) over a test
+    dataloader: eval mode, no_grad."""
     def prob_fn(batch):
-        if isinstance(model, FusionModule):
-            x, _, _, site, age, sex = model._unpack(batch)
-            logits, _ = model(x, age, sex, site)
-        else:
-            logits = model(model._unpack(batch)[0])
-        return torch.sigmoid(logits.float().flatten())
+        return torch.sigmoid(model.features_and_logits(batch)[1].float().flatten())
 
     was_training = model.training
     model.eval()

@@ -23,10 +23,10 @@ linear probe (reference LinearProbeCallback.py:72-85: sklearn's
 LogisticRegression, balanced_accuracy_score and roc_auc_score) on the features'
 device; see their docstrings.
 
-BinaryMetricsDevice is the baselines' epoch accumulator for accuracy, precision,
-recall, F1 and AUROC with its state on the device (csrc/binmetric_ops.hip: integer
-counts, one 48-byte read per compute()); binary_metrics_from_counts is the host
-arithmetic it shares with OnlyImagingModule's binary_metrics.
+BinaryMetrics / binary_metrics are the baselines' epoch accumulator for accuracy,
+precision, recall, F1 and AUROC on the host; BinaryMetricsDevice keeps its state on
+the device (csrc/binmetric_ops.hip: integer counts, one 48-byte read per compute()).
+Both finish with the host arithmetic of binary_metrics_from_counts.
 
 grouped_binary_counts and subgroup_metrics_from_counts are the test-set evaluation
 (reference scripts/test_eval_downstream.py: six sklearn metrics overall and per
@@ -547,6 +547,54 @@ def binary_metrics_from_counts(tp, fp, fn, tn, u2):
     return {"accuracy": acc, "precision": prec, "recall": rec, "f1": f1, "auroc": auroc}
 
 
+class BinaryMetrics:
+    """Epoch accumulator for torchmetrics' Binary{Accuracy, Precision, Recall,
+    F1Score, AUROC} (threshold 0.5; precision / recall / F1 are 0 when their
+    denominator is 0, as torchmetrics' zero_division default)."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self._p, self._y = [], []
+
+    def update(self, probs, labels):
+        self._p.append(probs.detach().float().reshape(-1).cpu())
+        self._y.append(labels.detach().reshape(-1).cpu().long())
+
+    def compute(self):
+        if not self._p:
+            return {}
+        p, y = torch.cat(self._p), torch.cat(self._y)
+        return binary_metrics(p, y)
+
+
+def binary_metrics(p: torch.Tensor, y: torch.Tensor):
+    pred = (p >= 0.5).long()
+    tp = int(((pred == 1) & (y == 1)).sum())
+    fp = int(((pred == 1) & (y == 0)).sum())
+    fn = int(((pred == 0) & (y == 1)).sum())
+    tn = int(((pred == 0) & (y == 0)).sum())
+    npos, nneg = tp + fn, fp + tn
+    u2 = 0
+    if npos and nneg:
+        # Mann-Whitney U with average ranks for ties = the area under the ROC curve
+        order = torch.argsort(p.double())
+        ps = p.double()[order]
+        ranks = torch.empty_like(ps)
+        i, n = 0, ps.numel()
+        while i < n:
+            j = i
+            while j + 1 < n and ps[j + 1] == ps[i]:
+                j += 1
+            ranks[i:j + 1] = 0.5 * (i + j) + 1.0
+            i = j + 1
+        r = torch.empty_like(ranks)
+        r[order] = ranks
+        u2 = 2.0 * float(r[y == 1].sum() - npos * (npos + 1) / 2)   # ranks are half-integers: exact
+    return binary_metrics_from_counts(tp, fp, fn, tn, u2)
+
+
 def binary_pair_counts_cpu(scores: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int]:
     """(wins, ties) of csrc/binmetric_ops.hip's pair count in plain torch: over i with
     labels[i] == 1 and j with labels[j] == 0, #{scores[i] > scores[j]} and
@@ -562,7 +610,7 @@ def binary_pair_counts_cpu(scores: torch.Tensor, labels: torch.Tensor) -> Tuple[
 
 
 class BinaryMetricsDevice:
-    """BinaryMetrics (src/models/baseline/OnlyImagingModule.py) with its state on the scores'
+    """BinaryMetrics (above) with its state on the scores'
     device: reset(), update(probs, labels), compute() -> the same five keys, {} when empty.
 
     The scores (fp32) and labels (uint8) of an epoch sit in two buffers that double through torch
