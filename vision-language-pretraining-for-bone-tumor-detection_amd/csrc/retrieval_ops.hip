@@ -20,7 +20,9 @@ __device__ __forceinline__ bool tk_before(float a, int ia, float b, int ib) {
 
 // One wave per row.  Each lane keeps its best kTopK in a descending register
 // list (compare-swap chain, no dynamic indexing); then K rounds of a
-// wave-wide (value, index) max pop the heads.
+// wave-wide (value, index) max pop the heads.  NaN is out of contract, but a
+// NaN is never selected: it fails both compares of tk_before, so it is never
+// inserted and the result is the top-K of the row's other entries.
 __global__ void __launch_bounds__(256) row_topk_kernel(int R, int N, const float* __restrict__ x, long long ldx,
                                                        int K, float* __restrict__ vals, int* __restrict__ idx) {
   const int lane = threadIdx.x & 63;

@@ -202,6 +202,17 @@ def _pad_rows4(t):
     return t if r == 0 else torch.cat([t, t.new_zeros((r,) + tuple(t.shape[1:]))])
 
 
+_SORT_ROWS = 1024   # rows per sort of _stable_top: its temporaries stay at 12 B x 1024 x N beside the N x N matrix
+
+
+def _stable_top(sim, k):
+    """The first k column indices of every row of sim in descending order, ties to
+    the lower index: vlp_row_topk's rule, from a stable sort (torch.topk leaves the
+    order of equal values unspecified)."""
+    return torch.cat([torch.sort(c, dim=1, descending=True, stable=True).indices[:, :k]
+                      for c in sim.split(_SORT_ROWS)])
+
+
 class _LogitsFn(torch.autograd.Function):
     """logits = clamp(exp(logit_scale), max=100) * img @ txt^T (:456-459)."""
 
@@ -552,39 +563,42 @@ class VisionLanguageModule(_Base):
     def precision_at_k_on_image_embeddings(self, image_embeddings, labels, ks: list) -> dict:
         """:364-400.  On the GPU the top-(k+1) lists come from chunked fp32
         similarity GEMMs + vlp_row_topk (no N x N matrix); the first entry (the
-        query itself) is dropped as in the reference."""
+        query itself) is dropped as in the reference.
+
+        Equal similarities rank by index, the lower first, on the kernel path and
+        on the fallback (off the GPU, or k + 1 > 16: the full matrix and a stable
+        sort), so a k's value does not depend on which other ks are asked for.
+        The reference selects with torch.topk, which leaves tie order unspecified.
+        With exact duplicates of a row the dropped first entry is the lowest-index
+        copy, which need not be the query."""
         assert all(k + 1 <= image_embeddings.shape[0] for k in ks), "k+1 must be less than or equal to the batch size"
         e = torch.nn.functional.normalize(image_embeddings.float())
         labels = labels.to(e.device)
         out = {}
         if e.is_cuda and max(ks) + 1 <= 16:
             _, top_all = ops.sim_topk(e, e, max(ks) + 1)
-            for k in ks:
-                correct = (labels.unsqueeze(1) == labels[top_all[:, 1:k + 1]]).sum(dim=1)
-                out[k] = (correct.float() / k).mean().item()
-            return out
-        sim = e @ e.T
+        else:
+            top_all = _stable_top(e @ e.T, max(ks) + 1)
         for k in ks:
-            top = sim.topk(k=k + 1, dim=1).indices[:, 1:]
-            correct = (labels.unsqueeze(1) == labels[top]).sum(dim=1)
+            correct = (labels.unsqueeze(1) == labels[top_all[:, 1:k + 1]]).sum(dim=1)
             out[k] = (correct.float() / k).mean().item()
         return out
 
     def recall_at_k_on_image_text_retreival(self, image_embeddings, text_embeddings, ks: list) -> dict:
-        """:402-439 (GPU: chunked similarity + vlp_row_topk, as above)."""
+        """:402-439 (GPU: chunked similarity + vlp_row_topk, as above).  Equal
+        similarities rank by index, the lower first, on the kernel path and on the
+        fallback alike: of duplicate captions the earlier one is retrieved first.
+        The reference's torch.topk leaves tie order unspecified."""
         i = torch.nn.functional.normalize(image_embeddings.float())
         t = torch.nn.functional.normalize(text_embeddings.float())
         out = {}
         tgt = torch.arange(i.shape[0], device=i.device)
         if i.is_cuda and max(ks) <= 16:
             _, top_all = ops.sim_topk(i, t, max(ks))
-            for k in ks:
-                out[k] = (top_all[:, :k] == tgt.unsqueeze(1)).any(dim=1).sum().item() / i.shape[0]
-            return out
-        sim = i @ t.T
+        else:
+            top_all = _stable_top(i @ t.T, max(ks))
         for k in ks:
-            top = sim.topk(k=k, dim=1).indices
-            out[k] = (top == tgt.unsqueeze(1)).any(dim=1).sum().item() / i.shape[0]
+            out[k] = (top_all[:, :k] == tgt.unsqueeze(1)).any(dim=1).sum().item() / i.shape[0]
         return out
 
     def evaluate_downstream_precision_at_k(self, mode="entire") -> Tuple[dict, dict]:
