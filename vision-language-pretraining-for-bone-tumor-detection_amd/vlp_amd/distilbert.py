@@ -3,9 +3,8 @@
 TextEncoder, src/models/pretrain/VisionLanguageModule.py:43, :57-60: the
 reference's default text encoder; the CLS hidden state is the sentence embedding).
 
-The encoder block is the post-LN BERT block TinyBertTower drives, so this
-tower reuses its forward / backward drivers and only maps names.  What differs
-(transformers modeling_distilbert):
+The encoder block is the post-LN BERT block PostLNTextTower drives (text_tower.py),
+so this module only declares what is DistilBERT's (transformers modeling_distilbert):
   * parameter names and their order are HF DistilBertModel's (embeddings.*,
     transformer.layer.{i}.{attention.{q,k,v,out}_lin, sa_layer_norm,
     ffn.{lin1,lin2}, output_layer_norm}); no token-type table, no pooler;
@@ -17,10 +16,7 @@ Query/key/value weights are contiguous in the arena (then their biases), so one
 """
 from __future__ import annotations
 
-import torch
-import torch.nn as nn
-
-from .tinybert import TinyBertTower, _Holder
+from .text_tower import PostLNTextTower
 
 
 class DistilBertConfig:
@@ -38,7 +34,7 @@ class DistilBertConfig:
         self.attention_dropout = float(attention_dropout)
 
 
-class DistilBertTower(TinyBertTower):
+class DistilBertTower(PostLNTextTower):
     _LAYER = "transformer.layer.{}."
     _N = {"q": "attention.q_lin", "k": "attention.k_lin", "v": "attention.v_lin",
           "ao": "attention.out_lin", "ln1": "sa_layer_norm",
@@ -48,62 +44,4 @@ class DistilBertTower(TinyBertTower):
     _HF_PREFIX = "distilbert."
 
     def __init__(self, config: DistilBertConfig = None, compute_dtype: str = "bf16", device=None):
-        nn.Module.__init__(self)
-        cfg = config or DistilBertConfig()
-        self.cfg = cfg
-        self.compute_dtype = compute_dtype
-        D, F, N = cfg.hidden, cfg.ffn, self._N
-        specs = [("embeddings.word_embeddings.weight", (cfg.vocab_size, D)),
-                 ("embeddings.position_embeddings.weight", (cfg.max_pos, D)),
-                 ("embeddings.LayerNorm.weight", (D,)), ("embeddings.LayerNorm.bias", (D,))]
-        order = []   # HF registration order (q, k, v, out interleave weight / bias), not the arena's
-        for i in range(cfg.layers):
-            p = self._LAYER.format(i)
-            # q/k/v weights then q/k/v biases: contiguous for the fused QKV GEMM
-            specs += [(p + N[n] + ".weight", (D, D)) for n in ("q", "k", "v")]
-            specs += [(p + N[n] + ".bias", (D,)) for n in ("q", "k", "v")]
-            specs += [(p + N["ao"] + ".weight", (D, D)), (p + N["ao"] + ".bias", (D,)),
-                      (p + N["ln1"] + ".weight", (D,)), (p + N["ln1"] + ".bias", (D,)),
-                      (p + N["fc1"] + ".weight", (F, D)), (p + N["fc1"] + ".bias", (F,)),
-                      (p + N["fc2"] + ".weight", (D, F)), (p + N["fc2"] + ".bias", (D,)),
-                      (p + N["ln2"] + ".weight", (D,)), (p + N["ln2"] + ".bias", (D,))]
-            order += [p + N[n] + s for n in ("q", "k", "v", "ao", "ln1", "fc1", "fc2", "ln2")
-                      for s in (".weight", ".bias")]
-        self._init_arena_packed(specs, device)
-        for name, _ in specs[:4]:
-            self._register_path(name)
-        for name in order:
-            self._register_path(name)
-        self.reset_parameters()
-        self._seed = 0x5EED
-        self._ws = {}
-
-    def _register_path(self, full):
-        """Register arena view `full` as a parameter at its dotted path, creating
-        the holder modules on the way (a numbered child makes its parent a
-        ModuleList, as in HF's `transformer.layer`)."""
-        parts = full.split(".")
-        owner = self
-        for j, part in enumerate(parts[:-1]):
-            nxt = owner._modules.get(part)
-            if nxt is None:
-                nxt = nn.ModuleList() if parts[j + 1].isdigit() else _Holder()
-                owner.add_module(part, nxt)
-            owner = nxt
-        self._register(owner, parts[-1], full)
-
-    @torch.no_grad()
-    def reset_parameters(self):
-        """HF DistilBertPreTrainedModel._init_weights: N(0, 0.02) weights/embeddings,
-        zero biases, LayerNorm 1/0 (the 1-D weights are the LayerNorm gains)."""
-        for name, (o, n, shape) in self.arena.layout.items():
-            v = self.arena.view(name)
-            if name.endswith("bias"):
-                v.zero_()
-            elif len(shape) == 1:
-                v.fill_(1.0)
-            else:
-                v.normal_(0.0, 0.02)
-
-    def grads_for_autograd(self, existing=None):
-        return super(TinyBertTower, self).grads_for_autograd()   # no pooler to leave out
+        super().__init__(config or DistilBertConfig(), compute_dtype, device)
